@@ -1,8 +1,25 @@
 """Headline benchmark: scored pairs/s + ILD-eval users/s, 1M users x 10M items,
 d=128, top-100 (BASELINE.json metric; configs[3], the 10M-item catalog).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: it generates the tables,
+runs W warmup steps, times exactly K steps, writes the last timed step's
+outputs when --dump-outputs is given, and prints the result line. Everything
+else the line can carry is measured only with ``--full``: the achievable-peak
+probes before and after the timed region (`peak_achievable*` in the roofline
+objects), `cpu_baseline`, the float64 `check` of the timed lists and, at
+N >= 4, `grid_alt`. The same holds for the secondary workloads' CPU baselines
+and probes.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller
+as DIR/scores.npy (float32), DIR/items.npy (the item ids, float64) and
+DIR/ild.npy (float32): the top-k lists of a fixed, seeded sample of users
+(sorted user order) and the ILD of every user, below 64 MB in all. The tables
+are seeded, so equal arguments give equal inputs, and two builds can be
+compared file by file. With more than one rank each rank writes its own users
+as DIR/<name>_rank<r>.npy.
 
 One step = one pass of the hot path over the whole synthetic workload:
   score_topk (bf16 MFMA scores of every user of this rank's user slice x every
@@ -12,8 +29,8 @@ One step = one pass of the hot path over the whole synthetic workload:
 Ranks form a (N/S) x S grid (divrec.distributed.grid_layout): the S ranks of
 a row row-shard the item table contiguously and share one user slice. S =
 --item-shards (default N: pure 8-way item row-sharding at N=8, the north-star
-layout). At N >= 4 the (N/2) x 2 grid is timed too and reported beside the
-line as `grid_alt` (fewer, longer item shards: less survivor work per rank).
+layout). With --full at N >= 4 the (N/2) x 2 grid is timed too and reported beside
+the line as `grid_alt` (fewer, longer item shards: less survivor work per rank).
 Inputs are resident in HBM before timing (the item table is also replicated
 for the ILD gathers); the total work is fixed, so scaling is "strong".
 value = U*I / step time (max over ranks).
@@ -22,7 +39,7 @@ Rank 0 prints ONE JSON line. The `roofline` object is for the dominant kernel
 (score_topk: bound = MFMA, achieved = 2*U*I_shard*d flop / average HIP-event
 time of the call on its stream); `traffic` comes from a committed rocprofv3 PMC
 summary (profiles/pmc_traffic.json) when one exists for this exact config.
-`cpu_baseline` (N=1 only) times the reference's per-user loop restated in
+`cpu_baseline` (--full, N=1 only) times the reference's per-user loop restated in
 torch (oracle.reference_loop_topk: set difference, torch.full, embedding
 gather + sum(u*i), argsort, slice) on all of this host's CPU share, on a
 bounded user sample, with the vectorised torch GEMM + topk beside it.
@@ -47,6 +64,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "diversity-recommendations_amd"))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -96,7 +114,16 @@ def parse():
     ap.add_argument("--candidates", type=int, default=1000, help="mmr: top-C candidates per user")
     ap.add_argument("--mmr-k", type=int, default=100, help="mmr: re-ranked list length")
     ap.add_argument("--mmr-lambda", type=float, default=0.5)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="catalog workload: write the last timed step's outputs (top-k scores "
+                         "and item ids of a seeded user sample, every user's ILD) as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: achievable-peak "
+                         "probes, CPU baselines, the float64 list check, the alternative grid")
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload != "catalog":
+        ap.error("--dump-outputs is for the default (catalog) workload")
+    return args
 
 
 def gen_table(rows: int, d: int, seed: int, device, block: int = 1 << 20) -> torch.Tensor:
@@ -184,6 +211,7 @@ def cpu_baseline(U: torch.Tensor, I: torch.Tensor, recs: torch.Tensor, k: int, b
     }
 
 
+FULL = False  # --full: main() sets it; the probes below are runs of their own and need it
 _PEAKS = None
 _PEAK_COLD = None  # the MFMA probe run before any timed work (a cold chip)
 
@@ -232,6 +260,8 @@ def cold_mfma_probe(dev):
     yet run the sustained scan (the probe after the timed
     scan runs on a hot, clocked-down chip and flatters the fraction)."""
     global _PEAK_COLD
+    if not FULL:
+        return None
     lib = _probe_lib()
     if lib is not None and _PEAK_COLD is None:
         _PEAK_COLD = _mfma_probe_tflops(lib, dev)
@@ -273,7 +303,10 @@ def with_measured(roof: dict, dev, key: str) -> dict:
     MFMA: the box's own back-to-back bf16 MFMA loop on random operands (the
     clock it holds under that load is below the one the 2.5 PF spec assumes).
     HBM: the guide's measured 6.29 TB/s copy rate (this repo's probe copy,
-    reported beside it, reaches less: a lower bound, not the ceiling)."""
+    reported beside it, reaches less: a lower bound, not the ceiling).
+    Without --full the object is returned as it is (no probe runs)."""
+    if not FULL:
+        return roof
     pk = achievable_peaks(dev)
     if key == "hbm_copy_gbs":
         roof["peak_achievable"] = HBM_ACHIEVABLE_GBS
@@ -538,11 +571,36 @@ def time_layout(args, world: int, dev, S: int, record_recs: bool = True):
     return {"lay": lay, "S": S, "dt": float(t[0]), "ild_max": float(t[1]),
             "topk_max": float(t[2]), "topk_s": topk_s, "users": users, "items": items,
             "recs": recs if record_recs else None, "scores": scores if record_recs else None,
+            "ild": ild if record_recs else None,
             "u_lo": u_lo, "u_hi": u_hi, "lo": lo, "hi": hi}
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs writes less than this in all
+DUMP_SEED = 20240
+
+
+def dump_outputs(path: str, scores: torch.Tensor, recs: torch.Tensor, ild: torch.Tensor,
+                 rank: int, world: int) -> None:
+    """--dump-outputs: the (scores, item ids, ILD) the last timed step returned,
+    as float32 / float64 / float32 .npy files. The lists take 3/4 of the byte
+    budget: all users if they fit, else a seeded sample in user order; the ILD
+    is written whole when it fits in the rest, else for the same sample."""
+    n, k = recs.shape
+    rows = min(n, DUMP_BYTES * 3 // 4 // (k * (4 + 8)))
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    sel = torch.sort(torch.randperm(n, generator=g)[:rows]).values.to(recs.device)
+    ild_sel = ild if n * 4 <= DUMP_BYTES // 4 else ild[sel]
+    tag = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    for name, t, dt in (("scores", scores[sel], torch.float32), ("items", recs[sel], torch.float64),
+                        ("ild", ild_sel, torch.float32)):
+        np.save(os.path.join(path, f"{name}{tag}.npy"), t.to(dt).cpu().numpy())
+
+
 def main():
+    global FULL
     args = parse()
+    FULL = args.full
     if args.workload in ("catalog", "mmr"):  # the multi-GPU workloads
         rc = maybe_launch(args)
         if rc is not None:
@@ -572,6 +630,8 @@ def main():
     U_n, I_n, d, k = args.users, args.items, args.dim, args.k
     step_s = r["dt"] / args.steps
     u_lo, u_hi, lo, hi = r["u_lo"], r["u_hi"], r["lo"], r["hi"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r["scores"], r["recs"], r["ild"], rank, world)
 
     cfg_key = f"U{U_n}_I{I_n}_d{d}_k{k}_G{world}"
     idb = r["recs"].element_size() if r["recs"] is not None else 4  # id bytes the ILD reads
@@ -630,14 +690,14 @@ def main():
     if args.check_users > 0:
         result["check"] = check_lists(args, r["lay"], r["users"], r["items"], r["recs"], u_lo,
                                       U_n, k, world)
-    elif world == 1 and args.fp64_check_users > 0:
+    elif args.full and world == 1 and args.fp64_check_users > 0:
         # the timed call's own lists on its own tables, against float64
         # (outside the timed region)
         sel = check_user_sample(U_n, I_n, d, k, args.fp64_check_users)
         result["check"] = fp64_gap_check(r["users"], r["items"], r["scores"], r["recs"], sel, k)
         if not result["check"]["ok"]:
             print(f"fp64 list check FAILED: {result['check']}", file=sys.stderr, flush=True)
-    if world >= 4 and world % 2 == 0 and S != 2 and not args.no_alt_grid:
+    if args.full and world >= 4 and world % 2 == 0 and S != 2 and not args.no_alt_grid:
         # the (N/2) x 2 grid beside the main layout: same work,
         # 2-way item shards, users split N/2 ways
         del r
@@ -659,7 +719,7 @@ def main():
         ild_roof = with_measured(result["ild_roofline"], dev, "hbm_copy_gbs")
         if ild_roof.get("probe_copy_gbs"):
             ild_roof["frac_of_probe_copy"] = ild_roof["achieved"] / ild_roof["probe_copy_gbs"]
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(r["users"], r["items"], r["recs"], k,
                                               args.cpu_budget_s)
     if rank == 0:
@@ -811,7 +871,7 @@ def secondary(args):
     dev = torch.device("cuda", 0)
     cold_mfma_probe(dev)  # before any timed work
     g = torch.Generator(device=dev).manual_seed(1234)
-    want_cpu = not args.no_cpu_baseline
+    want_cpu = args.full and not args.no_cpu_baseline
 
     if args.workload == "score1m":
         U_n, I_n, d, k = 1_000_000, 1_000_000, 64, 100
@@ -1213,7 +1273,7 @@ def ml100k(args, dev, g):
     torch.cuda.synchronize()
     wall = (time.perf_counter() - t0) / args.steps
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, ROOT)
         import oracle
 
@@ -1316,7 +1376,7 @@ def mmr_pipeline(args):
     per_user = C * d * 2 + C * 8 + kout * 4  # candidate rows + (id, score) + picks
     flops = 2.0 * n_r * I_n * d
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, ROOT)
         import oracle
 

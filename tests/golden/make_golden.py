@@ -288,7 +288,10 @@ def main():
         ent = metrics.EntropyDiversityScore(dataset=full_ds)(te, recs)
         pri = metrics.PRI(dataset=full_ds)(te, recs)
         mapk = metrics.MeanAveragePrecisionAtKScore()(te, recs)
-    save("ml100k_d100", U=U, I=I, train=tr, test=te, recs=recs, ild=res[0], precision=prec,
+    # the tables go into a file of their own (the tests' load() merges the two)
+    # so that each fixture stays below 1 MiB
+    save("ml100k_d100_tables", U=U, I=I)
+    save("ml100k_d100", train=tr, test=te, recs=recs, ild=res[0], precision=prec,
          recall=rec, ap=ap, ndcg=ndcg, entropy=ent, pri=pri, map=mapk)
 
 

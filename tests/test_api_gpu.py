@@ -27,7 +27,11 @@ DEV = torch.device("cuda", 0)
 
 
 def load(name):
-    return np.load(os.path.join(GOLD, f"{name}.npz"), allow_pickle=False)
+    g = np.load(os.path.join(GOLD, f"{name}.npz"), allow_pickle=False)
+    tables = os.path.join(GOLD, f"{name}_tables.npz")  # U and I, stored apart (file size)
+    if os.path.exists(tables):
+        g = {**g, **np.load(tables, allow_pickle=False)}
+    return g
 
 
 def mf_from(U, I, device=DEV):

@@ -272,6 +272,48 @@ def test_fp64_gap_check_rule_on_cpu():
     assert not bench.fp64_gap_check(U, I, off, i.int(), sel, k, chunk=1000, extra=8)["ok"]
 
 
+def test_bench_dump_outputs_and_full_option(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs) on the CPU: float32 scores, float64
+    item ids (exact) and float32 ILD; small outputs are written whole, large
+    ones as the same seeded user sample on every call, under the byte budget.
+    --full is off by default, and without it the probes do not run."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+
+    g = torch.Generator().manual_seed(6)
+    n, k = 300, 7
+    s = torch.randn(n, k, generator=g)
+    i = torch.randint(0, 1 << 30, (n, k), generator=g, dtype=torch.int32)
+    ild = torch.rand(n, generator=g)
+    bench.dump_outputs(str(tmp_path / "a"), s, i, ild, 0, 1)
+    got = {f: np.load(tmp_path / "a" / f"{f}.npy") for f in ("scores", "items", "ild")}
+    assert got["scores"].dtype == np.float32 and got["items"].dtype == np.float64
+    assert got["ild"].dtype == np.float32
+    assert np.array_equal(got["scores"], s.numpy()) and np.array_equal(got["ild"], ild.numpy())
+    assert np.array_equal(got["items"].astype(np.int64), i.long().numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1200)  # 900 B for the lists: 10 users; ILD: 300 B
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), s, i, ild, 1, 2)
+    b = {f: np.load(tmp_path / "b" / f"{f}_rank1.npy") for f in ("scores", "items", "ild")}
+    c = {f: np.load(tmp_path / "c" / f"{f}_rank1.npy") for f in ("scores", "items", "ild")}
+    assert all(np.array_equal(b[f], c[f]) for f in b)
+    assert b["scores"].shape == (10, k) and b["items"].shape == (10, k) and b["ild"].shape == (10,)
+    assert sum(a.nbytes for a in b.values()) <= 1200
+    rows = [int(np.flatnonzero((s.numpy() == r).all(1))[0]) for r in b["scores"]]
+    assert rows == sorted(rows) and len(set(rows)) == 10
+    assert np.array_equal(b["items"].astype(np.int64), i.long().numpy()[rows])
+    assert np.array_equal(b["ild"], ild.numpy()[rows])
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 2
+    assert bench.FULL is False and bench.cold_mfma_probe(None) is None
+    roof = {"achieved": 1.0}
+    assert bench.with_measured(roof, None, "mfma_bf16_tflops") == {"achieved": 1.0}
+
+
 def test_embedding_distance_device_copy_follows_its_table():
     """EmbeddingDistance keeps its bf16, zero-padded copy between calls and
     rebuilds it when the source changes in a way torch records (in-place

@@ -13,7 +13,11 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def load(name):
-    return np.load(os.path.join(GOLD, f"{name}.npz"), allow_pickle=False)
+    g = np.load(os.path.join(GOLD, f"{name}.npz"), allow_pickle=False)
+    tables = os.path.join(GOLD, f"{name}_tables.npz")  # U and I, stored apart (file size)
+    if os.path.exists(tables):
+        g = {**g, **np.load(tables, allow_pickle=False)}
+    return g
 
 
 @pytest.mark.parametrize("d", [32, 64, 128])
@@ -48,7 +52,7 @@ def test_recommendations_raw_fp32(name):
     against the reference's (torch order) — equal except at near-ties."""
     g = load(name)
     U, I = g["U"], g["I"]
-    k = int(g["k"]) if "k" in g.files else 10
+    k = int(g["k"]) if "k" in g else 10
     frozen = _frozen(g["train"], U.shape[0])
     recs = oracle.recommend_topk(U, I, k, frozen=frozen)
     bad = gap_check(recs, g["recs"], U, I, oracle.exclusion_csr(frozen), fp32_row_tol(U, I))
