@@ -49,14 +49,23 @@ using dr::f32x16;
 #define DG_T0(v) const uint64_t v = __builtin_amdgcn_s_memtime()
 #define DG_ADD(slot, t0) dg[slot] += __builtin_amdgcn_s_memtime() - (t0)
 #define DG_CNT(slot) dg[slot] += 1
+#define DG_MARK(mark) dg[mark] = __builtin_amdgcn_s_memtime()
+#define DG_SINCE(slot, mark) dg[slot] += __builtin_amdgcn_s_memtime() - dg[mark]
 #else
 #define DG_T0(v) ((void)0)
 #define DG_ADD(slot, t0) ((void)0)
 #define DG_CNT(slot) ((void)0)
+#define DG_MARK(mark) ((void)0)
+#define DG_SINCE(slot, mark) ((void)0)
 #endif
+// The stage boundary is split in four: the exact-count vmcnt wait, the
+// barrier wait, the refill's DMA issue, and the stretch from the end of
+// boundary() to the first MFMA of the stage (kDgBFirst, also part of kDgMma;
+// kDgBMark holds its start stamp).
 enum {
   kDgTotal, kDgPrologue, kDgBoundary, kDgMma, kDgHits, kDgEnqueue, kDgDrain, kDgFlush,
-  kDgNTiles, kDgNEnqueue, kDgNDrain, kDgNFlush, kDgNStages, kDgRealtime, kDgSlots = 16
+  kDgNTiles, kDgNEnqueue, kDgNDrain, kDgNFlush, kDgNStages, kDgRealtime,
+  kDgBWait, kDgBBarrier, kDgBIssue, kDgBFirst, kDgBMark, kDgSlots = 24
 };
 
 // Geometry. Every alternative measured against these values lost and was
@@ -229,27 +238,46 @@ __device__ __forceinline__ int64_t uni64(int64_t v) {
 // opaque, so hipcc cannot hoist 64-bit per-lane addresses out of the tile loop
 // (they cost registers the loop does not have, and their spill reloads wait
 // vmcnt(0), draining the ring).
-template <int D, int CAP>
+// LANE_ONCE (the bf16 d = 128 scans): one instruction covers THREADS / CPR =
+// 32 rows, a whole tile, so a lane's 16-B chunk and the swizzle of its row are
+// the same in every instruction of the stage. They are computed once per
+// stage and three VALU per instruction are left (row, clamp, offset) of the
+// general form's nine: the refill sits in the stage boundary, where no wave
+// of the CU has an MFMA in flight (DESIGN.md §3.1 "The stage boundary").
+template <int D, int CAP, bool LANE_ONCE>
 __device__ __forceinline__ void issue_stage(const char* __restrict__ I, int64_t n_items,
                                             int64_t row0, uint32_t lds_stage) {
   using G = TileGeom<D, CAP>;
   constexpr int ROWS = G::SR * kTileItems;
+  static_assert(!LANE_ONCE || (G::THREADS % G::CPR == 0 && (G::THREADS / G::CPR) % 32 == 0 &&
+                               64 % G::CPR == 0),
+                "an instruction covers whole 32-row tiles");
   uint32_t tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   const int lane = (int)(tid & 63u);
   const int wave = (int)(__builtin_amdgcn_readfirstlane(threadIdx.x) >> 6);
   // readfirstlane: the base is wave-uniform; the asm takes it as an SGPR pair
   const char* base = reinterpret_cast<const char*>(uni64((int64_t)(I + row0 * (2 * D))));
-  const int64_t left = n_items - 1 - row0;
+  const int64_t left = n_items - 1 - row0;  // >= 0: a stage starts inside the slice
   const int rmax = left < ROWS - 1 ? (int)left : ROWS - 1;
+  // LANE_ONCE: this lane's row in instruction 0 and its swizzled chunk's byte offset
+  const uint32_t r0 = ((uint32_t)wave * 64u + (uint32_t)lane) / (uint32_t)G::CPR;
+  const uint32_t lcb = (((uint32_t)lane % (uint32_t)G::CPR) ^ (uint32_t)G::swz((int)(r0 & 31u))) * 16u;
 #pragma unroll
   for (int j = 0; j < G::LPT; ++j) {
     const int wave_first = j * G::THREADS + wave * 64;  // wave-uniform chunk index
-    const int idx = wave_first + lane;
-    const int r = idx / G::CPR;
-    const int lc = (idx % G::CPR) ^ G::swz(r & 31);
-    const int rr = r < rmax ? r : rmax;
-    const uint32_t off = (uint32_t)(rr * (2 * D) + lc * 16);
+    uint32_t off;
+    if constexpr (LANE_ONCE) {
+      const uint32_t r = r0 + (uint32_t)(j * (G::THREADS / G::CPR));
+      const uint32_t rr = r < (uint32_t)rmax ? r : (uint32_t)rmax;
+      off = rr * (uint32_t)(2 * D) + lcb;
+    } else {
+      const int idx = wave_first + lane;
+      const int r = idx / G::CPR;
+      const int lc = (idx % G::CPR) ^ G::swz(r & 31);
+      const int rr = r < rmax ? r : rmax;
+      off = (uint32_t)(rr * (2 * D) + lc * 16);
+    }
     const uint32_t m0 = __builtin_amdgcn_readfirstlane(lds_stage + wave_first * 16);
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -677,6 +705,7 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
   constexpr int kRing = G::RING;
   constexpr int kStageBytes = G::STAGE_BYTES;
   constexpr int kLpt = G::LPT;
+  constexpr bool kLaneOnce = W == 128 && !F32;  // issue_stage's per-stage lane addressing
   constexpr int RING_BYTES = kRing * kStageBytes;
   // per wave: per-user key counts, radix histogram, staged survivor blocks
   // (16 scores + one 8-B record: tile | slot | h, threshold)
@@ -824,6 +853,7 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
         if (s + 1 < KS) lds_wait1(af[s]);
         else lds_wait0(af[s]);
         if (s + 2 < KS) af[s + 2] = ds_read_b128_asm(tb + a_off(s + 2));
+        if (s == 0 && t == stage_t0 && g0 == 0) DG_SINCE(kDgBFirst, kDgBMark);
         kstep_mma<F32, NG>(af[s], bfr, g0, s, acc);
       }
     };
@@ -961,21 +991,28 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
       DG_T0(t_b);
       stage_t0 = st * SR;
       if (vs[0] > vm_done) wait_vmcnt_dyn(vmc - vs[0]);
+      DG_ADD(kDgBWait, t_b);
+      DG_T0(t_bb);
       __builtin_amdgcn_s_barrier();
+      DG_ADD(kDgBBarrier, t_bb);
 #pragma unroll
       for (int i = 0; i + 1 < kRing - 1; ++i) vs[i] = vs[i + 1];
       if (st + kRing - 1 < nst) {
-        issue_stage<D, CAP>(a.I, a.n_items, i_beg + (int64_t)(st + kRing - 1) * SR * kTileItems,
-                       lds_ring + ((st + kRing - 1) % kRing) * kStageBytes);
+        DG_T0(t_i);
+        issue_stage<D, CAP, kLaneOnce>(a.I, a.n_items,
+                                       i_beg + (int64_t)(st + kRing - 1) * SR * kTileItems,
+                                       lds_ring + ((st + kRing - 1) % kRing) * kStageBytes);
         vmc += kLpt;
+        DG_ADD(kDgBIssue, t_i);
       }
       vs[kRing - 2] = vmc;
       DG_ADD(kDgBoundary, t_b);
       DG_CNT(kDgNStages);
+      DG_MARK(kDgBMark);
     };
     for (int st = 0; st < kRing - 1 && st < nst; ++st) {
-      issue_stage<D, CAP>(a.I, a.n_items, i_beg + (int64_t)st * SR * kTileItems,
-                     lds_ring + st * kStageBytes);
+      issue_stage<D, CAP, kLaneOnce>(a.I, a.n_items, i_beg + (int64_t)st * SR * kTileItems,
+                                     lds_ring + st * kStageBytes);
       vmc += kLpt;
 #pragma unroll
       for (int i = 0; i < kRing - 1; ++i)

@@ -24,7 +24,10 @@ import torch  # noqa: E402
 from divrec import _backend as B  # noqa: E402
 
 SLOTS = ["total", "prologue", "boundary", "mma_issue", "hits", "enqueue", "drain", "flush",
-         "n_tiles", "n_enqueue", "n_drain", "n_flush", "n_stages", "realtime_100mhz"]
+         "n_tiles", "n_enqueue", "n_drain", "n_flush", "n_stages", "realtime_100mhz",
+         "b_vmcnt_wait", "b_barrier_wait", "b_dma_issue", "b_exit_to_first_mfma"]
+NSLOT = 24  # kDgSlots (csrc/score_scan.h)
+BOUNDARY = SLOTS[14:18]  # the stage boundary's four parts
 
 
 def main():
@@ -65,14 +68,16 @@ def main():
     off = fn(args.users, args.items, B.DR_BF16, args.dim, args.k, ctypes.byref(grid))
     # the kernel aligns the workspace base up to 256 B
     base = (-ws.data_ptr()) % 256
-    blk = ws[base + off: base + off + grid.value * 8 * 16 * 8].view(torch.int64).cpu()
-    recs = blk.view(grid.value * 8, 16).tolist()
+    blk = ws[base + off: base + off + grid.value * 8 * NSLOT * 8].view(torch.int64).cpu()
+    recs = blk.view(grid.value * 8, NSLOT).tolist()
     tot = [sum(r[i] for r in recs) for i in range(len(SLOTS))]
     res = {"kernel_ms": ms, "waves": len(recs)}
     for i, nm in enumerate(SLOTS):
         res[nm] = tot[i] / max(1, len(recs))
     cyc = res["total"]
-    res["shares"] = {nm: round(res[nm] / cyc, 4) for nm in SLOTS[1:8]}
+    res["shares"] = {nm: round(res[nm] / cyc, 4) for nm in SLOTS[1:8] + BOUNDARY}
+    res["boundary_cycles_per_stage"] = {nm: round(res[nm] / max(1, res["n_stages"]), 1)
+                                        for nm in ["boundary"] + BOUNDARY}
     res["tflops"] = 2.0 * args.users * args.items * args.dim / (ms * 1e-3) / 1e12
     res["cycles_per_tile"] = cyc / max(1, res["n_tiles"])
     # in-kernel shader clock: s_memtime cycles / s_memrealtime ticks (100 MHz)
@@ -83,6 +88,9 @@ def main():
         sel = [r for i, r in enumerate(recs) if i % 8 in half]
         t = [sum(r[i] for r in sel) / max(1, len(sel)) for i in range(len(SLOTS))]
         res[name] = {nm: round(t[i] / max(1.0, t[0]), 4) for i, nm in enumerate(SLOTS[1:8], 1)}
+        res[name].update({nm: round(t[14 + i] / max(1.0, t[0]), 4) for i, nm in enumerate(BOUNDARY)})
+        res[name]["cycles_per_stage"] = {nm: round(t[14 + i] / max(1.0, t[12]), 1)
+                                         for i, nm in enumerate(BOUNDARY)}
     print(json.dumps(res))
 
 

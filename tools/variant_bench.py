@@ -132,7 +132,8 @@ def main():
         same = bool(torch.equal(outs[t][1], ref_i) and torch.equal(outs[t][0], ref_s))
         ok &= same
         med = statistics.median(times[t])
-        res["variants"][t] = {"median_ms": med, "min_ms": min(times[t]),
+        res["variants"][t] = {"median_ms": med, "min_ms": min(times[t]), "max_ms": max(times[t]),
+                              "rounds_ms": [round(x, 2) for x in times[t]],
                               "tflops": flop / (med * 1e-3) / 1e12, "identical": same,
                               "guess_failures": fails.get(t)}
     print(json.dumps(res), flush=True)
