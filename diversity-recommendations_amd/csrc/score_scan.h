@@ -16,6 +16,9 @@
 //     stage; the LDS image is
 //     XOR-swizzled through the per-lane source address so the A-fragment
 //     ds_read_b128s are bank-conflict-free. All 8 waves share every stage.
+//     In the bf16 d = 128 scans with 72-KB stages waves 0-3 issue the whole
+//     refill (18 instructions each) and waves 4-7 none: the younger wave of
+//     each SIMD is the stage's critical path (half_issue, boundary()).
 //     A fragments are read two k-steps ahead of the MFMAs that use them.
 //   * The 32x32 MFMAs put items on M and users on N, so a lane holds 16 scores
 //     of ONE user: the hot epilogue is a 16-way max and one compare with that
@@ -126,18 +129,34 @@ constexpr int stage_bytes_for(int w, int cap) {
 constexpr int kRingNarrow = 2;  // ring slots for d <= 64
 constexpr int ring_for(int w) { return w == 128 ? kRingWide : (w <= 64 ? kRingNarrow : kRingOther); }
 
-template <int D, int CAP>  // D = W, the row's width in bf16 units (row bytes / 2)
+// Which scans leave the ring refill to waves 0-3 (TileGeom::ISSUERS = 4; the
+// comment at the kernel's boundary() has the why): the bf16 d = 128 main
+// scans and rescans with 72-KB stages. One-process A/B against eight issuers
+// (profiles/refill_half/): -1.4 to -2.2 % at 1M x 10M, k = 100, -0.9 % at
+// 1M x 1.25M; the mirror image (waves 4-7 issue) +0.35 % at the headline.
+// Kept on eight issuers: the staged long-list instance (k = 1000: -0.9 % on
+// one machine, +0.3 to +0.7 % in three records on another), d <= 64 (config 2:
+// inside the parent arm's spread), the sample scans (1 % of the headline
+// step: no A/B resolves them), fp32 and d >= 256 (not measured).
+constexpr bool half_issue(int w, int cap, bool f32, bool gmax) {
+  return w == 128 && !f32 && !gmax && !long_staged(w, cap);
+}
+
+// D = W, the row's width in bf16 units (row bytes / 2); HALF: half_issue()
+template <int D, int CAP, bool HALF = false>
 struct TileGeom {
   static constexpr int WAVES = waves_for(D);
   static constexpr int THREADS = WAVES * 64;
+  static constexpr int ISSUERS = HALF ? 4 : WAVES;       // waves that issue the ring refill
   static constexpr int STAGE_BYTES = stage_bytes_for(D, CAP);  // one LDS ring slot
   static constexpr int RING = ring_for(D);                // slots (RING - 1 stages in flight)
-  static constexpr int LPT = STAGE_BYTES / 16 / THREADS;  // LDS-DMA per thread per stage
+  // LDS-DMA instructions per issuing wave per stage (one moves 64 * 16 B)
+  static constexpr int LPT = STAGE_BYTES / 16 / (ISSUERS * 64);
   static constexpr int KSTEPS = D / 16;                 // MFMA k-steps per row
   static constexpr int CPR = D / 8;                     // 16-B chunks per row
   static constexpr int TILE_BYTES = kTileItems * D * 2;
   static constexpr int SR = STAGE_BYTES / TILE_BYTES;   // row tiles per stage
-  static_assert(LPT >= 1 && STAGE_BYTES % (16 * THREADS) == 0, "stage geometry");
+  static_assert(LPT >= 1 && STAGE_BYTES % (16 * ISSUERS * 64) == 0, "stage geometry");
   static_assert(RING >= 2, "ring depth");
   static constexpr int RPB = (2 * D >= 256) ? 1 : 256 / (2 * D);  // rows per 256-B bank row
   static constexpr int SWM = (CPR < 16 ? CPR : 16) - 1;
@@ -238,24 +257,28 @@ __device__ __forceinline__ int64_t uni64(int64_t v) {
 // opaque, so hipcc cannot hoist 64-bit per-lane addresses out of the tile loop
 // (they cost registers the loop does not have, and their spill reloads wait
 // vmcnt(0), draining the ring).
-// LANE_ONCE (the bf16 d = 128 scans): one instruction covers THREADS / CPR =
-// 32 rows, a whole tile, so a lane's 16-B chunk and the swizzle of its row are
-// the same in every instruction of the stage. They are computed once per
-// stage and three VALU per instruction are left (row, clamp, offset) of the
-// general form's nine: the refill sits in the stage boundary, where no wave
-// of the CU has an MFMA in flight (DESIGN.md §3.1 "The stage boundary").
-template <int D, int CAP, bool LANE_ONCE>
+// The stage's 16-B chunks are dealt in rounds of one instruction per issuing
+// wave: instruction j of wave w moves chunks j * ISSUERS * 64 + w * 64 + lane
+// (1 KB, lane-linear in LDS at 16 * that index). Only waves < ISSUERS call.
+// LANE_ONCE (the bf16 d = 128 scans): an instruction moves 4 rows of 256 B
+// and a round ISSUERS * 64 / CPR rows (32 with eight issuers; 16 with four:
+// rows 16 j + 4 w + lane / 16), a multiple of the swizzle's period, so a
+// lane's 16-B chunk and the swizzle of its row are the same in every
+// instruction of the stage. They are computed once per stage and three VALU
+// per instruction are left (row, clamp, offset) of the general form's nine:
+// the refill sits at the stage boundary (DESIGN.md §3.1 "The stage boundary").
+template <int D, int CAP, bool LANE_ONCE, bool HALF>
 __device__ __forceinline__ void issue_stage(const char* __restrict__ I, int64_t n_items,
                                             int64_t row0, uint32_t lds_stage) {
-  using G = TileGeom<D, CAP>;
+  using G = TileGeom<D, CAP, HALF>;
   constexpr int ROWS = G::SR * kTileItems;
-  static_assert(!LANE_ONCE || (G::THREADS % G::CPR == 0 && (G::THREADS / G::CPR) % 32 == 0 &&
-                               64 % G::CPR == 0),
-                "an instruction covers whole 32-row tiles");
+  constexpr int ROUND = G::ISSUERS * 64;  // chunks per instruction round
+  static_assert(!LANE_ONCE || (64 % G::CPR == 0 && (ROUND / G::CPR) % (G::RPB * (G::SWM + 1)) == 0),
+                "a round's rows are a multiple of the swizzle period");
   uint32_t tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   const int lane = (int)(tid & 63u);
-  const int wave = (int)(__builtin_amdgcn_readfirstlane(threadIdx.x) >> 6);
+  const int wave = (int)(__builtin_amdgcn_readfirstlane(threadIdx.x) >> 6);  // < ISSUERS
   // readfirstlane: the base is wave-uniform; the asm takes it as an SGPR pair
   const char* base = reinterpret_cast<const char*>(uni64((int64_t)(I + row0 * (2 * D))));
   const int64_t left = n_items - 1 - row0;  // >= 0: a stage starts inside the slice
@@ -265,10 +288,10 @@ __device__ __forceinline__ void issue_stage(const char* __restrict__ I, int64_t 
   const uint32_t lcb = (((uint32_t)lane % (uint32_t)G::CPR) ^ (uint32_t)G::swz((int)(r0 & 31u))) * 16u;
 #pragma unroll
   for (int j = 0; j < G::LPT; ++j) {
-    const int wave_first = j * G::THREADS + wave * 64;  // wave-uniform chunk index
+    const int wave_first = j * ROUND + wave * 64;  // wave-uniform chunk index
     uint32_t off;
     if constexpr (LANE_ONCE) {
-      const uint32_t r = r0 + (uint32_t)(j * (G::THREADS / G::CPR));
+      const uint32_t r = r0 + (uint32_t)(j * (ROUND / G::CPR));
       const uint32_t rr = r < (uint32_t)rmax ? r : (uint32_t)rmax;
       off = rr * (uint32_t)(2 * D) + lcb;
     } else {
@@ -691,7 +714,8 @@ template <int W, int CAP, bool SEEDED, bool F32, bool GMAX = false>
 __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_scan_kernel(TopkArgs a) {
   static_assert(!(GMAX && SEEDED), "tile-max scans are the (unseeded) sample scans");
   constexpr int D = W;  // geometry is by row bytes: an fp32 row of d is a bf16 row of 2d
-  using G = TileGeom<D, CAP>;
+  constexpr bool kHalf = half_issue(W, CAP, F32, GMAX);  // waves 0-3 issue the whole ring refill
+  using G = TileGeom<D, CAP, kHalf>;
   constexpr int NU_T = nut_for(D);
   constexpr int NG = ngroup_for(D);  // user tiles per accumulator group
   constexpr int NGRP = NU_T / NG;    // groups scored against each item tile
@@ -734,6 +758,8 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
 
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
+  // wave-uniform, kept scalar: this wave issues (and counts, and waits for) ring refills
+  const bool issuer = !kHalf || (int)(__builtin_amdgcn_readfirstlane(threadIdx.x) >> 6) < G::ISSUERS;
   const int h = lane >> 5;
   const int col = lane & 31;
   char* wbase = smem + RING_BYTES + wave * WAVE_BYTES;
@@ -987,31 +1013,43 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
     // Stage boundary s: wait (exact count) for this wave's DMA of stage s, a
     // raw barrier publishes the whole stage, then stage s+kRing-1 is issued
     // into the slot of stage s-1, which every wave finished reading.
+    // kHalf: only waves 0-3 (`issuer`) issue the refill, count it (vmc, vs[])
+    // and wait for it; waves 4-7, the younger wave of each SIMD and the last
+    // to reach every barrier, keep vs[] = 0, so they wait for no VMEM here and
+    // leave the barrier straight into the first tile's ds_reads and MFMAs
+    // while their SIMD partners issue the DMA. Still correct:
+    //   RAW  a wave always relied on the barrier for the other waves' pieces
+    //        of the stage; waves 4-7 now rely on it for all pieces. An
+    //        issuer's vmcnt wait for its DMA still precedes its arrival.
+    //   WAR  the refill into the slot of stage s-1 is still issued only after
+    //        the barrier every wave reaches after its last read of that slot
+    //        (at the unit end: wait_vmcnt<0> and __syncthreads before the
+    //        next unit's prologue refill).
     auto boundary = [&](int st) {
       DG_T0(t_b);
       stage_t0 = st * SR;
       if (vs[0] > vm_done) wait_vmcnt_dyn(vmc - vs[0]);
-      DG_ADD(kDgBWait, t_b);
+      if (issuer) DG_ADD(kDgBWait, t_b);
       DG_T0(t_bb);
       __builtin_amdgcn_s_barrier();
       DG_ADD(kDgBBarrier, t_bb);
 #pragma unroll
       for (int i = 0; i + 1 < kRing - 1; ++i) vs[i] = vs[i + 1];
-      if (st + kRing - 1 < nst) {
+      if (issuer && st + kRing - 1 < nst) {
         DG_T0(t_i);
-        issue_stage<D, CAP, kLaneOnce>(a.I, a.n_items,
+        issue_stage<D, CAP, kLaneOnce, kHalf>(a.I, a.n_items,
                                        i_beg + (int64_t)(st + kRing - 1) * SR * kTileItems,
                                        lds_ring + ((st + kRing - 1) % kRing) * kStageBytes);
         vmc += kLpt;
         DG_ADD(kDgBIssue, t_i);
       }
-      vs[kRing - 2] = vmc;
+      if (issuer) vs[kRing - 2] = vmc;
       DG_ADD(kDgBoundary, t_b);
       DG_CNT(kDgNStages);
       DG_MARK(kDgBMark);
     };
-    for (int st = 0; st < kRing - 1 && st < nst; ++st) {
-      issue_stage<D, CAP, kLaneOnce>(a.I, a.n_items, i_beg + (int64_t)st * SR * kTileItems,
+    for (int st = 0; issuer && st < kRing - 1 && st < nst; ++st) {
+      issue_stage<D, CAP, kLaneOnce, kHalf>(a.I, a.n_items, i_beg + (int64_t)st * SR * kTileItems,
                                      lds_ring + st * kStageBytes);
       vmc += kLpt;
 #pragma unroll
