@@ -1,5 +1,6 @@
 from .base_datasets import (
     DevicePairWiseDataset,
+    DevicePointWiseDataset,
     PairWiseDataset,
     PairWiseRow,
     PointWiseDataset,
@@ -11,6 +12,7 @@ from .storages import Features, UserItemInteractionsDataset
 
 __all__ = [
     "DevicePairWiseDataset",
+    "DevicePointWiseDataset",
     "Features",
     "UserItemInteractionsDataset",
     "PairWiseRow",

@@ -8,6 +8,10 @@ PairWiseDataset draws its samples with Python ``random.choices`` over the same
 populations, in the same order, as the reference, so a seeded ``random``
 yields the same (user, positive, negative) triples.
 
+Opt-in device-resident streams, whole batches as device tensors:
+DevicePointWiseDataset (PointWiseDataset's rows) and DevicePairWiseDataset
+(PairWiseDataset's populations, sampled by dr_sample_pairwise).
+
 Divergences: RankingDataset accepts ``frozen=None`` (every
 item is a candidate) where the reference raises TypeError (:151,168).
 """
@@ -132,6 +136,67 @@ def _device_csr(data: UserItemInteractionsDataset, n_users: int, n_items: int, d
     rowptr = torch.zeros(n_users + 1, dtype=torch.int64, device=device)
     rowptr[1:] = torch.cumsum(counts, 0)
     return rowptr, items.to(torch.int32).contiguous()
+
+
+class DevicePointWiseDataset:
+    """PointWiseDataset resident on ``device``: ``loader`` yields whole batches
+    ``(user_id, item_id, None, None, true_relevance)`` as device tensors (int64
+    ids, targets in the dtype of ``interaction_scores``) with no per-row Python
+    (features are not gathered: the MF fast path ignores them).
+
+    Targets are ``interaction_scores[item_id]``, what PointWiseDataset yields
+    (the reference indexes the scores by item id, base_datasets.py:52), so with
+    ``shuffle=False`` the batches equal ``PointWiseDataset(data).loader(
+    batch_size=B)``'s element for element, the last short batch included.
+    ``by_row=True`` opts into ``interaction_scores[row]``, the score of each
+    interaction itself (a deliberate divergence).
+
+    ``shuffle=True``: each ``loader()`` call is a new epoch whose order is a
+    ``torch.randperm`` on the device seeded from ``(seed, epoch)``. Works with
+    ``device="cpu"`` too (only the training loops need the GPU)."""
+
+    def __init__(self, data: UserItemInteractionsDataset, device="cuda", seed: int = 0,
+                 by_row: bool = False):
+        self.data = data
+        self.device = torch.device(device)
+        self.seed = int(seed)
+        self.epoch = 0
+        self.by_row = bool(by_row)
+        inter = data.interactions.to(torch.int64)
+        scores = data.interaction_scores
+        if not by_row and inter.size(0) and int(inter[:, 1].max()) >= scores.size(0):
+            # PointWiseDataset fails at that row; checked here on the host so
+            # that no device gather ever reads outside the scores
+            raise IndexError(f"index {int(inter[:, 1].max())} is out of bounds for dimension 0 "
+                             f"with size {scores.size(0)} (interaction_scores[item_id])")
+        self.user_id = inter[:, 0].contiguous().to(self.device)
+        self.item_id = inter[:, 1].contiguous().to(self.device)
+        scores = scores.to(self.device)
+        self.true_relevance = scores if by_row else scores[self.item_id]
+
+    def __len__(self) -> int:
+        return self.user_id.numel()
+
+    def loader(self, batch_size: int = 1, shuffle: bool = False, drop_last: bool = False,
+               **_unused) -> Iterator[PointWiseRow]:
+        n, batch_size = len(self), int(batch_size)
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        cols = (self.user_id, self.item_id, self.true_relevance)
+        if shuffle:
+            g = torch.Generator(device=self.device)
+            g.manual_seed((self.seed * 0x9E3779B97F4A7C15 + self.epoch) & ((1 << 63) - 1))
+            self.epoch += 1
+            order = torch.randperm(n, device=self.device, generator=g)
+            cols = tuple(c[order] for c in cols)
+        end = n // batch_size * batch_size if drop_last else n
+
+        def batches():
+            for b0 in range(0, end, batch_size):
+                b1 = min(b0 + batch_size, end)
+                yield cols[0][b0:b1], cols[1][b0:b1], None, None, cols[2][b0:b1]
+
+        return batches()
 
 
 class DevicePairWiseDataset:

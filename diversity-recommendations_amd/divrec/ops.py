@@ -467,6 +467,61 @@ def bpr_fwd_bwd(
     return loss, hit
 
 
+# --------------------------------------------------------------------------- point-wise MSE
+def mse_fwd_bwd(
+    user_table: torch.Tensor,
+    item_table: torch.Tensor,
+    user_id: torch.Tensor,
+    item_id: torch.Tensor,
+    target: torch.Tensor,
+    grad_scale: float,
+    grad_user: Optional[torch.Tensor],
+    grad_item: Optional[torch.Tensor],
+    err: Optional[torch.Tensor] = None,
+    check: bool = True,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fused point-wise MSE forward + backward (dr_mse_fwd_bwd); returns
+    per-pair (pred fp32, loss fp32) with loss = (target - pred)^2 and
+    accumulates ``-2 (target - pred) grad_scale`` times the other side's row
+    into the dense grad_user / grad_item. Both gradient tables None is the
+    forward-only form (no atomics). Ids are range-checked on the device (an
+    invalid pair adds nothing and gets NaN): with ``check`` and no ``err`` the
+    call reads the count (one sync) and raises IndexError; otherwise the count
+    goes to the caller's ``err`` (may be None), checked by the caller
+    (point_wise_train_loop: once per epoch)."""
+    dev = B.require_device(user_table, item_table, user_id, item_id, target, grad_user, grad_item)
+    _need(user_table.dtype == torch.float32 and item_table.dtype == torch.float32, "fp32 tables")
+    _need(user_table.dim() == 2 and item_table.dim() == 2, "tables must be 2-D")
+    _need(user_table.size(1) == item_table.size(1), "tables must share embedding_dim")
+    _contig(user_table, "user_table"), _contig(item_table, "item_table")
+    for t in (user_id, item_id):
+        _need(t.dtype == torch.int64 and t.dim() == 1 and t.numel() == user_id.numel(),
+              "ids must be 1-D int64 of equal length")
+    n = user_id.numel()
+    _need(target.dtype == torch.float32 and target.dim() == 1 and target.numel() == n,
+          "target must be 1-D fp32, one per pair")
+    for g, t, nm in ((grad_user, user_table, "grad_user"), (grad_item, item_table, "grad_item")):
+        if g is not None:
+            _need(g.shape == t.shape and g.dtype == torch.float32 and g.is_contiguous(),
+                  f"{nm} must be a contiguous fp32 tensor shaped like its table")
+    user_id, item_id, target = user_id.contiguous(), item_id.contiguous(), target.contiguous()
+    pred = torch.empty(n, dtype=torch.float32, device=dev)
+    loss = torch.empty(n, dtype=torch.float32, device=dev)
+    own = err is None and check
+    if own:
+        err = B.error_counter(dev)
+    rc = B.lib().dr_mse_fwd_bwd(
+        user_table.data_ptr(), user_table.size(0), item_table.data_ptr(), item_table.size(0),
+        user_table.size(1), user_id.data_ptr(), item_id.data_ptr(),
+        target.data_ptr(), n, float(grad_scale), pred.data_ptr(), loss.data_ptr(),
+        B.ptr(grad_user), B.ptr(grad_item), B.ptr(err), B.stream(dev),
+    )
+    B.check(rc, "dr_mse_fwd_bwd")
+    if own:
+        B.raise_if_out_of_range(err, "dr_mse_fwd_bwd")
+    return pred, loss
+
+
 def adam_dense(
     param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
     lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int,

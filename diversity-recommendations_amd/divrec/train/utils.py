@@ -14,6 +14,9 @@ Same functions, arguments and return values as the reference. On the hot path:
   plain torch.optim.Adam (its state tensors are used and kept up to date, so
   the optimizer stays usable). Other combinations take the generic path: the
   model's HIP forward/backward under autograd and ``optimizer.step()``.
+* ``point_wise_train_loop`` with MatrixFactorization + MSELoss on fp32 targets
+  runs each batch as ONE dr_mse_fwd_bwd followed by the same optimizer steps,
+  and ``point_wise_score_loop`` with MSELoss losses as its forward-only form.
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ from divrec import _backend, ops
 from divrec.datasets import PairWiseDataset, PointWiseDataset, RankingDataset
 from divrec.losses import (
     LogSigmoidDifferenceLoss,
+    MSELoss,
     PairWiseLoss,
     PointWiseLoss,
     RecommendationsAwareLoss,
@@ -47,16 +51,51 @@ def _to(t, device):
 
 
 # --------------------------------------------------------------------------- scoring
+def _mse_pairs(model: MatrixFactorization, user_id, item_id, true_rel):
+    """The MSE fast paths' batch on the model's device: (uid, iid, target).
+    Host ids are range-checked here, before any compute; device ids are left
+    to the caller (a min/max read-back, or the kernel's error counter)."""
+    dev = model._device()
+    U, I = model.user_embeddings.weight, model.item_embeddings.weight
+    if user_id.device.type == "cpu":
+        _backend.host_ids_in_range(user_id, U.size(0), "user_id")
+    if item_id.device.type == "cpu":
+        _backend.host_ids_in_range(item_id, I.size(0), "item_id")
+    uid, iid = (t.to(dev, torch.int64, non_blocking=True) for t in (user_id, item_id))
+    return uid, iid, true_rel.to(dev, non_blocking=True)
+
+
+def _fp32_targets(true_rel) -> bool:
+    return isinstance(true_rel, torch.Tensor) and true_rel.dtype == torch.float32
+
+
 def point_wise_score_loop(dataset: PointWiseDataset, model: RankingModel,
                           losses: List[PointWiseLoss], **loader_params):
+    """With MatrixFactorization, MSELoss-only ``losses`` and fp32 targets each
+    batch is ONE forward-only dr_mse_fwd_bwd (no atomics) whose per-pair
+    squared errors every loss then reduces as it says; anything else scores
+    through the model's forward and ``loss.point_wise``."""
     model.eval()
     dev = _model_device(model)
     values = {loss.__class__.__name__: [] for loss in losses}
+    fast = bool(losses) and _mf_scoring(model) and all(type(loss) is MSELoss for loss in losses)
+    epoch_err = None  # id range errors of the kernel on device batches
     with torch.no_grad():
         for user_id, item_id, uf, itf, true_rel in dataset.loader(**loader_params):
+            if fast and _fp32_targets(true_rel):
+                uid, iid, target = _mse_pairs(model, user_id, item_id, true_rel)
+                if epoch_err is None:
+                    epoch_err = _backend.error_counter(uid.device)
+                _, sq = ops.mse_fwd_bwd(model.user_embeddings.weight.data,
+                                        model.item_embeddings.weight.data, uid, iid, target, 0.0,
+                                        None, None, err=epoch_err, check=False)
+                for loss in losses:
+                    values[loss.__class__.__name__].append(sq)
+                continue
             pred = model(user_id, item_id, uf, itf)
             for loss in losses:
                 values[loss.__class__.__name__].append(loss.point_wise(_to(true_rel, pred.device), pred))
+    _backend.raise_if_out_of_range(epoch_err, "point_wise_score_loop")
     return [loss.reduce_loss_values(torch.concatenate(values[loss.__class__.__name__]))
             for loss in losses]
 
@@ -154,23 +193,97 @@ def point_wise_train_loop(dataset: PointWiseDataset, model: RankingModel, loss: 
                           optimizer: torch.optim.Optimizer,
                           scores: Optional[List[PointWiseLoss]] = None,
                           **loader_params) -> Tuple[float, List[float]]:
+    """One epoch of point-wise training; returns (mean batch loss, [mean score]).
+
+    MatrixFactorization + a reducing MSELoss (+ MSELoss scores) on fp32 targets
+    runs each batch as ONE dr_mse_fwd_bwd (gather, squared error and dense
+    embedding gradients fused) followed by dr_adam_dense (plain Adam),
+    dr_adam_rows (SparseAdam) or ``optimizer.step()``, like the BPR path of
+    pair_wise_train_loop. Anything else is the reference's loop."""
     assert scores is None or all(score.reduce for score in scores)
     model.train()
-    batch_count, mean_loss = 0, 0.0
-    mean_scores = [0.0] * (len(scores) if scores is not None else 0)
+    n_scores = len(scores) if scores is not None else 0
+    # per batch: the loss and the scores, as Python floats (generic path) or
+    # as device tensors read back once after the epoch (fused path)
+    batch_losses, batch_scores = [], []
+    fused = _mse_fast_path(model, loss, scores)
+    adam = _plain_adam(optimizer)
+    lazy = fused and _plain_sparse_adam(optimizer)
+    epoch_err = None  # id range errors of the fused kernel
     for user_id, item_id, uf, itf, true_rel in dataset.loader(**loader_params):
-        pred = model(user_id, item_id, uf, itf)
-        true_rel = _to(true_rel, pred.device)
-        loss_value = loss(true_rel, pred)
-        loss_value.backward()
-        optimizer.step()
-        optimizer.zero_grad()
-        batch_count += 1
-        mean_loss += loss_value.item()
-        if scores is not None:
-            for i, score in enumerate(scores):
-                mean_scores[i] += score(true_rel, pred).item()
+        if fused and _fp32_targets(true_rel):
+            U, I = model.user_embeddings.weight, model.item_embeddings.weight
+            host = user_id.device.type == "cpu" and item_id.device.type == "cpu"
+            uid, iid, target = _mse_pairs(model, user_id, item_id, true_rel)
+            if not host and uid.numel():
+                # device batches: one min/max reduction read back (one sync)
+                # BEFORE the kernel, so a bad batch raises IndexError with the
+                # weights, the optimizer state and the gradient tables as they
+                # were (as in pair_wise_train_loop)
+                mm = torch.stack([uid.min(), uid.max(), iid.min(), iid.max()]).cpu().tolist()
+                if mm[0] < 0 or mm[1] >= U.size(0):
+                    raise IndexError("index out of range in self (user_id)")
+                if mm[2] < 0 or mm[3] >= I.size(0):
+                    raise IndexError("index out of range in self (item_id)")
+            if U.grad is None:
+                U.grad = torch.zeros_like(U)
+            if I.grad is None:
+                I.grad = torch.zeros_like(I)
+            if epoch_err is None:
+                epoch_err = _backend.error_counter(uid.device)
+            B = uid.numel()
+            grad_scale = 1.0 / B if loss.reduction == "mean" else 1.0
+            _, sq = ops.mse_fwd_bwd(U.data, I.data, uid, iid, target, grad_scale, U.grad, I.grad,
+                                    err=epoch_err, check=False)
+            if lazy:  # touched rows only; the kernel zeroes those gradient rows
+                lazy_adam_step(optimizer, {U: torch.unique(uid), I: torch.unique(iid)})
+            elif adam:
+                fused_adam_step(optimizer)
+                optimizer.zero_grad()
+            else:
+                optimizer.step()
+                optimizer.zero_grad()
+            batch_losses.append(loss.reduce_loss_values(sq))
+            if n_scores:  # MSELoss.point_wise = the squared errors, reduced as each score says
+                batch_scores.append(torch.stack([s.reduce_loss_values(sq) for s in scores]))
+        else:
+            pred = model(user_id, item_id, uf, itf)
+            true_rel = _to(true_rel, pred.device)
+            loss_value = loss(true_rel, pred)
+            loss_value.backward()
+            optimizer.step()
+            optimizer.zero_grad()
+            batch_losses.append(loss_value.item())
+            if n_scores:
+                batch_scores.append([score(true_rel, pred).item() for score in scores])
+    _backend.raise_if_out_of_range(epoch_err, "point_wise_train_loop")
+    # per-batch values added as Python floats in batch order, like the reference
+    batch_count, mean_loss = len(batch_losses), 0.0
+    mean_scores = [0.0] * n_scores
+    for value in _host_floats(batch_losses):
+        mean_loss += value
+    for row in _host_floats(batch_scores):
+        for i in range(n_scores):
+            mean_scores[i] += row[i]
     return mean_loss / batch_count, [s / batch_count for s in mean_scores]
+
+
+def _mse_fast_path(model, loss, scores) -> bool:
+    return (_mf_scoring(model) and type(loss) is MSELoss and loss.reduce
+            and (scores is None or all(type(s) is MSELoss for s in scores)))
+
+
+def _host_floats(values: list) -> list:
+    """``values`` with its device tensors (0-d or 1-D fp32) replaced by their
+    Python float (or list of floats), read back in one transfer."""
+    at = [k for k, v in enumerate(values) if isinstance(v, torch.Tensor)]
+    if not at:
+        return values
+    got = torch.stack([values[k] for k in at]).cpu().tolist()
+    out = list(values)
+    for k, v in zip(at, got):
+        out[k] = v
+    return out
 
 
 def _plain_adam(optimizer: torch.optim.Optimizer) -> bool:

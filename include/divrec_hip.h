@@ -274,6 +274,23 @@ int dr_bpr_fwd_bwd(const float* user_table, int64_t n_user_rows, const float* it
                    float grad_scale, float* loss, int32_t* hit, float* grad_user,
                    float* grad_item, int32_t* err, dr_stream_t stream);
 
+/* Point-wise MSE step (point_wise_train_loop, divrec/train/utils.py:108-115,
+ * with MSELoss, divrec/losses/mse_loss.py:6-10):
+ *   pred[b] = <U[u_b], I[i_b]>;  e = target[b] - pred[b];  loss[b] = e * e
+ *   g = -2 e * grad_scale  (grad_scale = 1/B for the 'mean' reduction, 1 for 'sum')
+ *   grad_user[u] += g I[i]; grad_item[i] += g U[u]
+ * fp32 tables [*, d], d in [1, 512]; ids int64 [B]; target fp32 [B]; pred and
+ * loss fp32 [B] may each be NULL. Gradients are DENSE fp32 tables accumulated
+ * with atomics; either may be NULL, and with both NULL the call is
+ * forward-only (no atomics: point_wise_score_loop, utils.py:19-24). A pair
+ * with an out-of-range id adds nothing, gets pred / loss NaN and counts in
+ * *err (id range checks, above). batch = 0 is a no-op. */
+int dr_mse_fwd_bwd(const float* user_table, int64_t n_user_rows, const float* item_table,
+                   int64_t n_item_rows, int64_t d, const int64_t* user_id,
+                   const int64_t* item_id, const float* target, int64_t batch,
+                   float grad_scale, float* pred, float* loss, float* grad_user,
+                   float* grad_item, int32_t* err, dr_stream_t stream);
+
 /* Dense Adam step in fp32 over n elements, the update torch.optim.Adam
  * (amsgrad=False, maximize=False) applies at divrec/train/utils.py:151:
  *   g = grad + weight_decay * param; m = lerp(m, g, 1 - beta1);
