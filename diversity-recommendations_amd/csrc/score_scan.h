@@ -7,7 +7,7 @@
 //   * W is the row width in bf16 units (row bytes / 2): a bf16 table of width d
 //     has W = d, an fp32 table W = 2d. Geometry (stages, user tiles, LDS
 //     swizzle, 16-B fragments) depends only on the row bytes, so both dtypes
-//     share it; only the MFMA differs (kstep_mma).
+//     share it; only the MFMA differs (kstep1).
 //   * Each wave keeps the rows of its NU_T*32 users resident in registers as
 //     MFMA B fragments for the whole scan.
 //   * Item rows go HBM -> LDS by LDS-DMA (global_load_lds_dwordx4) into a ring
@@ -85,10 +85,9 @@ enum {
 #endif
 constexpr int kStageBytesOther = 32768;  // ring slot for d = 256 / 512 (three slots)
 constexpr int kRingOther = 3;
-constexpr int kRingWide = 2;          // d = 128: two slots, one stage ahead
 constexpr int kNutWide = 4;           // user tiles of 32 per wave for d = 128
 constexpr int kNutNarrow = 8;         // for d <= 64 (+14 % at d = 64, 1M x 1M, against 4)
-constexpr int kFlushGapDefault = 96;  // new keys a buffer takes past k + kSlack before compaction
+constexpr int kFlushGap = 96;         // new keys a buffer takes past k + kSlack before compaction
 // Survivors are staged in LDS and resolved per stage for d <= 64 (twice as
 // dense per MFMA there: 4 % faster) and for d = 128 long lists (below),
 // stored directly for other d >= 128 (4 % faster there at k = 100).
@@ -97,11 +96,8 @@ constexpr int kStageBlocks = 64;  // staged lane blocks per wave (>= 64: one use
 // Waves per workgroup of a scan (one workgroup per CU): two per SIMD, 256
 // VGPRs each.
 constexpr int kWavesScan = 8;
-constexpr int waves_for(int) { return kWavesScan; }
-constexpr int kMaxWaves = kWavesScan;
 constexpr int kTileItems = 32;
 constexpr int kSlack = 32;  // keys kept beyond k by a compaction
-constexpr int kFlushGap = kFlushGapDefault;
 
 // Stage geometry per row width. d = 128: two 72-KB slots (one barrier per
 // 9 tiles; measured against three 32-KB slots: +2 % at 10M items, +6 % at
@@ -126,8 +122,8 @@ constexpr int stage_bytes_for(int w, int cap) {
   return long_staged(w, cap) ? kStageBytesLong
        : w == 128 ? DR_STAGE_BYTES_WIDE : (w <= 64 ? kStageBytesNarrow : kStageBytesOther);
 }
-constexpr int kRingNarrow = 2;  // ring slots for d <= 64
-constexpr int ring_for(int w) { return w == 128 ? kRingWide : (w <= 64 ? kRingNarrow : kRingOther); }
+// ring slots: two (one stage ahead) for d <= 128, three for wider rows
+constexpr int ring_for(int w) { return w <= 128 ? 2 : kRingOther; }
 
 // Which scans leave the ring refill to waves 0-3 (TileGeom::ISSUERS = 4; the
 // comment at the kernel's boundary() has the why): the bf16 d = 128 main
@@ -145,7 +141,7 @@ constexpr bool half_issue(int w, int cap, bool f32, bool gmax) {
 // D = W, the row's width in bf16 units (row bytes / 2); HALF: half_issue()
 template <int D, int CAP, bool HALF = false>
 struct TileGeom {
-  static constexpr int WAVES = waves_for(D);
+  static constexpr int WAVES = kWavesScan;
   static constexpr int THREADS = WAVES * 64;
   static constexpr int ISSUERS = HALF ? 4 : WAVES;       // waves that issue the ring refill
   static constexpr int STAGE_BYTES = stage_bytes_for(D, CAP);  // one LDS ring slot
@@ -343,6 +339,15 @@ __device__ __forceinline__ float max16(const f32x16& a) {
   return m;
 }
 
+// A user's max of a tile's 32 scores (the tile-max sample scans): the two
+// half-waves' 16-score maxima merged by v_permlane32_swap.
+__device__ __forceinline__ float max32(const f32x16& a) {
+  const float mh = max16(a);  // a value (stored): maxNum, NaN scores skipped
+  const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mh), __float_as_uint(mh),
+                                                   false, false);
+  return fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+}
+
 // The hot test's max: IEEE-754-2019 maximum (gfx950 v_maximum3_f32: NaN
 // propagates, no operand canonicalisation), 8 VALU per tile instead of 10.
 // Only ever compared through hot(): a NaN max counts as a hit, so the exact
@@ -356,6 +361,21 @@ __device__ __forceinline__ float hot_max16(const f32x16& a) {
 }
 // "some score of the tile may beat thr": a superset of `max > thr` (NaN = hit)
 __device__ __forceinline__ bool hot(float m, float thr) { return !(m <= thr); }
+
+// Item row (within its tile) of score register r of a lane of half-wave h.
+__device__ __forceinline__ int score_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+// The partial-tile rule: bit r is set iff score register r is a row of the
+// slice, `left` rows of which remain from the tile's first (all 16 but in the
+// slice's last tile, whose rows past the end repeat the last row).
+__device__ __forceinline__ uint32_t valid_rows(int64_t left, int h) {
+  uint32_t vmask = 0xffffu;
+  if (left < kTileItems) {
+    vmask = 0u;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) vmask |= (score_row(r, h) < (int)left ? 1u : 0u) << r;
+  }
+  return vmask;
+}
 
 struct CompactResult {
   int kept;
@@ -493,6 +513,9 @@ __device__ __noinline__ CompactResult compact_buffer_chunked(uint64_t* __restric
 // the CAP = 512 scans (k <= 224), whose footprint this exact code fixes
 // (the chunked form measured slower at d = 64, and letting it keep chunk 0
 // in registers spilled the d = 64 tile loop).
+// Its radix levels repeat the chunked form's on purpose: with the level loop
+// (or only its bucket pick) in a shared inline helper, the d = 128 CAP 2048
+// scan (k = 1000) measured +0.2 to +0.3 % (profiles/scan_dedupe/).
 template <int P>
 __device__ __noinline__ CompactResult compact_buffer_resident(uint64_t* __restrict__ buf, int n_in, int k,
                                                      int slack, const int32_t* __restrict__ ex,
@@ -583,32 +606,24 @@ __device__ __noinline__ CompactResult compact_buffer_resident(uint64_t* __restri
   return res;
 }
 
-// One k-step (one 16-B A fragment per lane) against NG user tiles.
-//   bf16: one v_mfma_f32_32x32x16_bf16 per tile (lane (col, h) holds row col,
+// One k-step (one 16-B A fragment per lane) against one user tile.
+//   bf16: one v_mfma_f32_32x32x16_bf16 (lane (col, h) holds row col,
 //         k = 16s + 8h .. +7).
 //   fp32: the same 16 B are four floats k = 8s + 4h + j, j = 0..3; four
-//         v_mfma_f32_32x32x2_f32 per tile, MFMA j summing k = 8s + j and
-//         8s + 4 + j over the two lane halves. The user fragment holds the
-//         same k, so every product of the row pair is taken once. The result
-//         is an exact fp32 fmaf chain (cdna_hip_programming.md, FP32-input MFMA).
-template <bool F32, int NG, int NB, int KS>
-__device__ __forceinline__ void kstep_mma(const u32x4& a, const u32x4 (&bfr)[NB][KS], int g0, int s,
-                                          f32x16 (&acc)[NG]) {
+//         v_mfma_f32_32x32x2_f32, MFMA j summing k = 8s + j and 8s + 4 + j
+//         over the two lane halves. The user fragment holds the same k, so
+//         every product of the row pair is taken once. The result is an
+//         exact fp32 fmaf chain (cdna_hip_programming.md, FP32-input MFMA).
+template <bool F32>
+__device__ __forceinline__ f32x16 kstep1(const u32x4& av, const u32x4& bv, f32x16 acc) {
   if constexpr (F32) {
-    const dr::f32x4 av = __builtin_bit_cast(dr::f32x4, a);
+    const dr::f32x4 a4 = __builtin_bit_cast(dr::f32x4, av), b4 = __builtin_bit_cast(dr::f32x4, bv);
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int ut = 0; ut < NG; ++ut) {
-        const dr::f32x4 bv = __builtin_bit_cast(dr::f32x4, bfr[g0 + ut][s]);
-        acc[ut] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc[ut], 0, 0, 0);
-      }
+    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[j], b4[j], acc, 0, 0, 0);
+    return acc;
   } else {
-#pragma unroll
-    for (int ut = 0; ut < NG; ++ut)
-      acc[ut] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                        __builtin_bit_cast(bf16x8, bfr[g0 + ut][s]),
-                                                        acc[ut], 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av),
+                                                   __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
   }
 }
 
@@ -711,7 +726,7 @@ __host__ __device__ inline DevSplit dev_split_plan(int64_t nb, int64_t grid, int
 }
 
 template <int W, int CAP, bool SEEDED, bool F32, bool GMAX = false>
-__global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_scan_kernel(TopkArgs a) {
+__global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_kernel(TopkArgs a) {
   static_assert(!(GMAX && SEEDED), "tile-max scans are the (unseeded) sample scans");
   constexpr int D = W;  // geometry is by row bytes: an fp32 row of d is a bf16 row of 2d
   constexpr bool kHalf = half_issue(W, CAP, F32, GMAX);  // waves 0-3 issue the whole ring refill
@@ -735,7 +750,7 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
   // (16 scores + one 8-B record: tile | slot | h, threshold)
   constexpr bool STAGED = D <= 64 || long_staged(D, CAP);
   constexpr int SB = STAGED ? kStageBlocks : 0;
-  // stage_hits resolves a full stage area, then stages up to 64 lanes of one
+  // stage_ut resolves a full stage area, then stages up to 64 lanes of one
   // user tile: the area must hold a whole wave's worth of blocks
   static_assert(!STAGED || SB >= 64, "staging area smaller than a wave");
   static_assert(!STAGED || NU_T * 32 <= 256, "staged slot field is 8 bits");
@@ -864,9 +879,13 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
     DG_ADD(kDgPrologue, t_pro);
 
     // -------------------------------------------------------------- MFMA tile
+    // LDS byte address of item tile t of the unit in the ring
+    auto tile_lds = [&](int t) -> uint32_t {
+      return lds_ring + ((t / SR) % kRing) * kStageBytes + (t % SR) * G::TILE_BYTES;
+    };
     auto mma_tile = [&](int t, f32x16 (&acc)[NG], auto GI) {
       constexpr int g0 = decltype(GI)::value * NG;
-      const uint32_t tb = lds_ring + ((t / SR) % kRing) * kStageBytes + (t % SR) * G::TILE_BYTES;
+      const uint32_t tb = tile_lds(t);
 #pragma unroll
       for (int ut = 0; ut < NG; ++ut) acc[ut] = f32x16{};
       // Fragment s is read two k-steps before its MFMAs; each wait retires
@@ -880,7 +899,8 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
         else lds_wait0(af[s]);
         if (s + 2 < KS) af[s + 2] = ds_read_b128_asm(tb + a_off(s + 2));
         if (s == 0 && t == stage_t0 && g0 == 0) DG_SINCE(kDgBFirst, kDgBMark);
-        kstep_mma<F32, NG>(af[s], bfr, g0, s, acc);
+#pragma unroll
+        for (int ut = 0; ut < NG; ++ut) acc[ut] = kstep1<F32>(af[s], bfr[g0 + ut][s], acc[ut]);
       }
     };
 
@@ -948,63 +968,60 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
     // call and no queue in the hot loop, so nothing forces the accumulators
     // and B fragments out of registers. A stage adds at most MARGIN keys per
     // user, so a buffer compacted at the stage end never overflows.
+    // enqueue_ut is one user tile u of the group. gbase (the item tile's first
+    // item id) and vmask (valid_rows) belong to the item tile and are passed
+    // in: recomputed per user tile they took the d = 128 CAP 512 / 1024 scans
+    // from 12-13 spilled VGPRs and 64 B of scratch to 20 and 96 B.
+    auto enqueue_ut = [&](const f32x16& ac, auto UI, uint32_t gbase, uint32_t vmask) {
+      constexpr int u = decltype(UI)::value;
+      uint32_t mask = 0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mask |= (ac[r] > thr[u] ? 1u : 0u) << r;
+      mask &= vmask;
+      const int slot = u * 32 + col;
+      uint64_t* ubuf = cbase + (size_t)slot * CAP;  // this lane's user buffer
+      // Common case: every hitting lane holds ONE survivor. It is then the
+      // lane's maximum (all other scores are <= thr < it), so one round
+      // stores it without the 16-way value select. Full tiles only (the
+      // max of a partial tile may sit in a row past the slice end).
+      if (vmask == 0xffffu && __ballot((mask & (mask - 1u)) != 0u) == 0ull) {
+        if (__ballot(mask != 0u) != 0ull) {
+          float m = max16(ac);
+          if (mask != 0u) {
+            const int row = score_row(__builtin_ctz(mask), h);
+            const uint32_t pos = atomicAdd(&ucnt[slot], 1u);
+            if (pos < (uint32_t)CAP) st64(ubuf + pos, dr::make_key(m, gbase + (uint32_t)row));
+          }
+          vmc += 1;  // the store above issued once (some lane had a key)
+        }
+        return;
+      }
+      while (__ballot(mask != 0u) != 0ull) {
+        const bool has = mask != 0u;
+        const int r = has ? __builtin_ctz(mask) : 0;
+        mask &= mask - 1u;
+        float v = ac[0];
+#pragma unroll
+        for (int q = 1; q < 16; ++q) v = (r == q) ? ac[q] : v;
+        const int row = score_row(r, h);
+        if (has) {
+          const uint32_t pos = atomicAdd(&ucnt[slot], 1u);
+          if (pos < (uint32_t)CAP)  // always true (flush_at + MARGIN <= CAP): a guard only
+            st64(ubuf + pos, dr::make_key(v, gbase + (uint32_t)row));
+        }
+        vmc += 1;  // the store above issued once (some lane had a key)
+      }
+    };
     auto enqueue = [&](int t, f32x16 (&acc)[NG], const uint64_t (&hb)[NG], auto GI) {
       constexpr int g0 = decltype(GI)::value * NG;
       DG_T0(t_e);
       const int64_t tile0 = i_beg + (int64_t)t * kTileItems;
-      const int valid = (int)((i_end - tile0) < kTileItems ? (i_end - tile0) : kTileItems);
       const uint32_t gbase = (uint32_t)(a.item_base + tile0);
-      uint32_t vmask = 0xffffu;  // rows past the slice end (last tile only)
-      if (valid < kTileItems) {
-        vmask = 0u;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-          vmask |= (row < valid ? 1u : 0u) << r;
-        }
-      }
-#pragma unroll
-      for (int ut = 0; ut < NG; ++ut) {
-        if (hb[ut] == 0ull) continue;
-        uint32_t mask = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mask |= (acc[ut][r] > thr[g0 + ut] ? 1u : 0u) << r;
-        mask &= vmask;
-        const int slot = (g0 + ut) * 32 + col;
-        uint64_t* ubuf = cbase + (size_t)slot * CAP;  // this lane's user buffer
-        // Common case: every hitting lane holds ONE survivor. It is then the
-        // lane's maximum (all other scores are <= thr < it), so one round
-        // stores it without the 16-way value select. Full tiles only (the
-        // max of a partial tile may sit in a row past the slice end).
-        if (vmask == 0xffffu && __ballot((mask & (mask - 1u)) != 0u) == 0ull) {
-          if (__ballot(mask != 0u) != 0ull) {
-            float m = max16(acc[ut]);
-            if (mask != 0u) {
-              const int r = __builtin_ctz(mask);
-              const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-              const uint32_t pos = atomicAdd(&ucnt[slot], 1u);
-              if (pos < (uint32_t)CAP) st64(ubuf + pos, dr::make_key(m, gbase + (uint32_t)row));
-            }
-            vmc += 1;  // the store above issued once (some lane had a key)
-          }
-          continue;
-        }
-        while (__ballot(mask != 0u) != 0ull) {
-          const bool has = mask != 0u;
-          const int r = has ? __builtin_ctz(mask) : 0;
-          mask &= mask - 1u;
-          float v = acc[ut][0];
-#pragma unroll
-          for (int q = 1; q < 16; ++q) v = (r == q) ? acc[ut][q] : v;
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-          if (has) {
-            const uint32_t pos = atomicAdd(&ucnt[slot], 1u);
-            if (pos < (uint32_t)CAP)  // always true (flush_at + MARGIN <= CAP): a guard only
-              st64(ubuf + pos, dr::make_key(v, gbase + (uint32_t)row));
-          }
-          vmc += 1;  // the store above issued once (some lane had a key)
-        }
-      }
+      const uint32_t vmask = valid_rows(i_end - tile0, h);
+      static_for<0, NG>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        if (hb[j] != 0ull) enqueue_ut(acc[j], IC<g0 + j>{}, gbase, vmask);
+      });
       DG_ADD(kDgEnqueue, t_e);
       DG_CNT(kDgNEnqueue);
     };
@@ -1130,7 +1147,7 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
         }
         } else {
         // four registers (one float4) at a time: few VGPRs, so this also runs
-        // inside stage_hits with the accumulators live
+        // inside stage_ut with the accumulators live
 #pragma unroll 1
         for (int q = 0; q < 4; ++q) {
           const float4 v4 = src[q];
@@ -1157,47 +1174,46 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
       DG_ADD(kDgDrain, t_d);
       DG_CNT(kDgNDrain);
     };
+    // stage_ut stages one user tile u: a block for every lane of `bal`.
+    auto stage_ut = [&](int t, const f32x16& ac, uint64_t bal, auto UI) {
+      constexpr int u = decltype(UI)::value;
+      // the lane's hit bit straight from the ballot's SGPR pair (s_and_saveexec
+      // on it; no VALU re-materialisation of the compare)
+      const bool hit = __builtin_amdgcn_inverse_ballot_w64(bal);
+      const int n = __popcll(bal);
+      if (nblk + n > SB) resolve(IC<0>{});  // rare (a scan's first stages): few registers
+      if (hit) {
+        const int i = nblk + lane_prefix(bal);
+        float4* dst = reinterpret_cast<float4*>(blk_val + i * 16);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          dst[q] = make_float4(ac[4 * q], ac[4 * q + 1], ac[4 * q + 2], ac[4 * q + 3]);
+        blk_meta[i] = make_uint2((uint32_t)(t - stage_t0) | ((uint32_t)(u * 32 + col) << 8) |
+                                     ((uint32_t)h << 16),
+                                 __float_as_uint(thr[u]));
+      }
+      nblk += n;
+    };
     auto stage_hits = [&](int t, f32x16 (&acc)[NG], const uint64_t (&hb)[NG], auto GI) {
       constexpr int g0 = decltype(GI)::value * NG;
       DG_T0(t_e);
-      const int64_t tile0 = i_beg + (int64_t)t * kTileItems;
-      const int valid = (int)((i_end - tile0) < kTileItems ? (i_end - tile0) : kTileItems);
-      const uint32_t gbase = (uint32_t)(a.item_base + tile0);
-#pragma unroll
-      for (int ut = 0; ut < NG; ++ut) {
-        const uint64_t bal = hb[ut];
-        if (bal == 0ull) continue;
-        // the lane's hit bit straight from the ballot's SGPR pair (s_and_saveexec
-        // on it; no VALU re-materialisation of the compare)
-        const bool hit = __builtin_amdgcn_inverse_ballot_w64(bal);
-        const int n = __popcll(bal);
-        if (nblk + n > SB) resolve(IC<0>{});  // rare (a scan's first stages): few registers
-        if (hit) {
-          const int i = nblk + lane_prefix(bal);
-          float4* dst = reinterpret_cast<float4*>(blk_val + i * 16);
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            dst[q] = make_float4(acc[ut][4 * q], acc[ut][4 * q + 1], acc[ut][4 * q + 2],
-                                 acc[ut][4 * q + 3]);
-          blk_meta[i] = make_uint2((uint32_t)(t - stage_t0) | ((uint32_t)((g0 + ut) * 32 + col) << 8) |
-                                       ((uint32_t)h << 16),
-                                   __float_as_uint(thr[g0 + ut]));
-        }
-        nblk += n;
-      }
+      static_for<0, NG>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        if (hb[j] != 0ull) stage_ut(t, acc[j], hb[j], IC<g0 + j>{});
+      });
       DG_ADD(kDgEnqueue, t_e);
       DG_CNT(kDgNEnqueue);
     };
     // Group-max enqueue (GMAX sample scans): one key per user and tile, the
-    // max of the tile's 32 scores of the user (the two half-waves' 16-score
-    // maxima merged by v_permlane32_swap). It is the whole epilogue of such a
-    // scan (the max is its hot test too). Lane h = 0 of a user appends its
-    // key; each user's LDS counter has that one writer, so its slot is a plain
-    // read and write (no atomic: one LDS round trip per user-tile group instead
-    // of one atomic per hitting half-wave, which also conflicted between the
-    // two halves of a user). A partial last tile (rows past the slice end
-    // repeat the last row) is skipped: leaving sample rows out only lowers the
-    // sample's order statistics, so the guess stays a lower bound.
+    // max of the tile's 32 scores of the user (max32). It is the whole
+    // epilogue of such a scan (the max is its hot test too). Lane h = 0 of a
+    // user appends its key; each user's LDS counter has that one writer, so
+    // its slot is a plain read and write (no atomic: one LDS round trip per
+    // user-tile group instead of one atomic per hitting half-wave, which also
+    // conflicted between the two halves of a user). A partial last tile (rows
+    // past the slice end repeat the last row) is skipped: leaving sample rows
+    // out only lowers the sample's order statistics, so the guess stays a
+    // lower bound.
     auto enqueue_gmax = [&](int t, f32x16 (&acc)[NG], auto GI) {
       constexpr int g0 = decltype(GI)::value * NG;
       DG_T0(t_e);
@@ -1208,10 +1224,7 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
       uint64_t any = 0ull;
 #pragma unroll
       for (int ut = 0; ut < NG; ++ut) {
-        const float mh = max16(acc[ut]);  // a value (stored): maxNum, NaN scores skipped
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mh), __float_as_uint(mh),
-                                                         false, false);
-        m[ut] = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+        m[ut] = max32(acc[ut]);
         if (a.gmax == 2) {  // dense tile maxima
           if (h == 0) dense_tmax(g0 + ut, t)[col] = m[ut];
           vmc += 1;
@@ -1236,6 +1249,35 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
         }
         vmc += 1;  // the store above issued once (some lane had a key)
       }
+      DG_ADD(kDgEnqueue, t_e);
+      DG_CNT(kDgNEnqueue);
+    };
+    // The same rule for one job of the per-user-tile pipeline. Kept beside the
+    // group form: folded into it (one form over N tiles, N = 1 here) the
+    // d <= 32 / 64 sample scans reload a spilled buffer address, with a
+    // vmcnt(0), at every store in the tile loop (none in this form), and the
+    // group form's batched counter read is part of the wide sample scans'
+    // instruction stream.
+    auto gmax_ut = [&](int t, const f32x16& ac, auto UI) {
+      constexpr int u = decltype(UI)::value;
+      const int64_t tile0 = i_beg + (int64_t)t * kTileItems;
+      const float m = max32(ac);
+      if (a.gmax == 2) {  // dense tile maxima: one 128-B store, no test
+        if (h == 0) dense_tmax(u, t)[col] = m;
+        vmc += 1;
+        return;
+      }
+      const uint64_t bal = __ballot(h == 0 && m > thr[u]);
+      if (bal == 0ull || i_end - tile0 < kTileItems) return;  // a partial last tile is skipped
+      DG_T0(t_e);
+      if (__builtin_amdgcn_inverse_ballot_w64(bal)) {
+        const int slot = u * 32 + col;
+        const uint32_t pos = ucnt[slot];  // one writer per user counter
+        ucnt[slot] = pos + 1u;
+        if (pos < (uint32_t)CAP)
+          st64(cbase + (size_t)slot * CAP + pos, dr::make_key(m, (uint32_t)(a.item_base + tile0)));
+      }
+      vmc += 1;  // the store above issued once (some lane had a key)
       DG_ADD(kDgEnqueue, t_e);
       DG_CNT(kDgNEnqueue);
     };
@@ -1275,7 +1317,7 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
     // (t, u + 1)'s chain is issued, so the test's max3 chain, compare and
     // ballot issue while this wave's own next MFMAs execute (an MFMA holds the
     // SIMD's vector issue for 8 of its 32 cycles) instead of after the whole
-    // group's chain has drained. A hit stages / enqueues the job before its
+    // group's chain has drained. A hit stages the job (stage_ut) before its
     // accumulator is reused two jobs later. The tile's A fragments are read
     // once (KS ds_read_b128 at the tile start) for all its NU_T jobs; the first
     // chain retires them one k-step at a time.
@@ -1283,21 +1325,11 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
     // (a chain of 8 k-steps already covers the group's hot test), and the fp32
     // d = 128 / bf16 d = 256 instances spill in the loop with it.
     constexpr bool UTP = NU_T % 2 == 0 && W <= 64;
+    static_assert(!UTP || STAGED, "the per-user-tile jobs stage their survivors");
     auto read_a = [&](int t, u32x4 (&af)[KS]) {
-      const uint32_t tb = lds_ring + ((t / SR) % kRing) * kStageBytes + (t % SR) * G::TILE_BYTES;
+      const uint32_t tb = tile_lds(t);
 #pragma unroll
       for (int s2 = 0; s2 < KS; ++s2) af[s2] = ds_read_b128_asm(tb + a_off(s2));
-    };
-    auto kstep1 = [&](const u32x4& av, const u32x4& bv, f32x16 acc) -> f32x16 {
-      if constexpr (F32) {
-        const dr::f32x4 a4 = __builtin_bit_cast(dr::f32x4, av), b4 = __builtin_bit_cast(dr::f32x4, bv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[j], b4[j], acc, 0, 0, 0);
-        return acc;
-      } else {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av),
-                                                       __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
-      }
     };
     // the tile's first chain: fragment s retired (lgkmcnt(KS - 1 - s), the
     // fragment named "+v") right before its k-step
@@ -1307,7 +1339,7 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
       static_for<0, KS>([&](auto SI) {
         constexpr int s2 = decltype(SI)::value;
         lds_waitn<KS - 1 - s2>(af[s2]);
-        acc = kstep1(af[s2], bfr[u][s2], acc);
+        acc = kstep1<F32>(af[s2], bfr[u][s2], acc);
         // keep each wait right before its k-step (hipcc would hoist the waits
         // together and wait for all but one fragment before the first MFMA)
         __builtin_amdgcn_sched_barrier(0);
@@ -1318,110 +1350,12 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
       constexpr int u = decltype(UI)::value;
       f32x16 acc = f32x16{};
 #pragma unroll
-      for (int s2 = 0; s2 < KS; ++s2) acc = kstep1(af[s2], bfr[u][s2], acc);
+      for (int s2 = 0; s2 < KS; ++s2) acc = kstep1<F32>(af[s2], bfr[u][s2], acc);
       return acc;
-    };
-    // staged survivors of one job (d <= 64): the hitting lanes' 16 scores
-    auto stage_ut = [&](int t, const f32x16& ac, uint64_t bal, auto UI) {
-      constexpr int u = decltype(UI)::value;
-      DG_T0(t_e);
-      const bool hit = __builtin_amdgcn_inverse_ballot_w64(bal);
-      const int n = __popcll(bal);
-      if (nblk + n > SB) resolve(IC<0>{});  // rare (a scan's first stages): few registers
-      if (hit) {
-        const int i = nblk + lane_prefix(bal);
-        float4* dst = reinterpret_cast<float4*>(blk_val + i * 16);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dst[q] = make_float4(ac[4 * q], ac[4 * q + 1], ac[4 * q + 2], ac[4 * q + 3]);
-        blk_meta[i] = make_uint2((uint32_t)(t - stage_t0) | ((uint32_t)(u * 32 + col) << 8) | ((uint32_t)h << 16),
-                                 __float_as_uint(thr[u]));
-      }
-      nblk += n;
-      DG_ADD(kDgEnqueue, t_e);
-      DG_CNT(kDgNEnqueue);
-    };
-    // direct survivors of one job (d >= 128): one key per lane per round
-    auto enqueue_ut = [&](int t, const f32x16& ac, auto UI) {
-      constexpr int u = decltype(UI)::value;
-      DG_T0(t_e);
-      const int64_t tile0 = i_beg + (int64_t)t * kTileItems;
-      const int valid = (int)((i_end - tile0) < kTileItems ? (i_end - tile0) : kTileItems);
-      const uint32_t gbase = (uint32_t)(a.item_base + tile0);
-      uint32_t vmask = 0xffffu;  // rows past the slice end (last tile only)
-      if (valid < kTileItems) {
-        vmask = 0u;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) vmask |= ((r & 3) + 8 * (r >> 2) + 4 * h < valid ? 1u : 0u) << r;
-      }
-      uint32_t mask = 0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mask |= (ac[r] > thr[u] ? 1u : 0u) << r;
-      mask &= vmask;
-      const int slot = u * 32 + col;
-      uint64_t* ubuf = cbase + (size_t)slot * CAP;
-      // every hitting lane holds ONE survivor (the common case, full tiles):
-      // it is the lane's maximum, stored without a value select
-      if (vmask == 0xffffu && __ballot((mask & (mask - 1u)) != 0u) == 0ull) {
-        if (__ballot(mask != 0u) != 0ull) {
-          const float m = max16(ac);
-          if (mask != 0u) {
-            const int r = __builtin_ctz(mask);
-            const uint32_t pos = atomicAdd(&ucnt[slot], 1u);
-            if (pos < (uint32_t)CAP)
-              st64(ubuf + pos, dr::make_key(m, gbase + (uint32_t)((r & 3) + 8 * (r >> 2) + 4 * h)));
-          }
-          vmc += 1;
-        }
-      } else {
-        while (__ballot(mask != 0u) != 0ull) {
-          const bool has = mask != 0u;
-          const int r = has ? __builtin_ctz(mask) : 0;
-          mask &= mask - 1u;
-          float v = ac[0];
-#pragma unroll
-          for (int q = 1; q < 16; ++q) v = (r == q) ? ac[q] : v;
-          if (has) {
-            const uint32_t pos = atomicAdd(&ucnt[slot], 1u);
-            if (pos < (uint32_t)CAP)
-              st64(ubuf + pos, dr::make_key(v, gbase + (uint32_t)((r & 3) + 8 * (r >> 2) + 4 * h)));
-          }
-          vmc += 1;
-        }
-      }
-      DG_ADD(kDgEnqueue, t_e);
-      DG_CNT(kDgNEnqueue);
-    };
-    // the sample scans' job (GMAX): the user's max of the tile's 32 scores
-    // (enqueue_gmax's rule for one user tile)
-    auto gmax_ut = [&](int t, const f32x16& ac, auto UI) {
-      constexpr int u = decltype(UI)::value;
-      const int64_t tile0 = i_beg + (int64_t)t * kTileItems;
-      const float mh = max16(ac);  // a value (stored): maxNum, NaN scores skipped
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mh), __float_as_uint(mh),
-                                                       false, false);
-      const float m = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-      if (a.gmax == 2) {  // dense tile maxima: one 128-B store, no test
-        if (h == 0) dense_tmax(u, t)[col] = m;
-        vmc += 1;
-        return;
-      }
-      const uint64_t bal = __ballot(h == 0 && m > thr[u]);
-      if (bal == 0ull || i_end - tile0 < kTileItems) return;  // a partial last tile is skipped
-      DG_T0(t_e);
-      if (__builtin_amdgcn_inverse_ballot_w64(bal)) {
-        const int slot = u * 32 + col;
-        const uint32_t pos = ucnt[slot];  // one writer per user counter
-        ucnt[slot] = pos + 1u;
-        if (pos < (uint32_t)CAP)
-          st64(cbase + (size_t)slot * CAP + pos, dr::make_key(m, (uint32_t)(a.item_base + tile0)));
-      }
-      vmc += 1;  // the store above issued once (some lane had a key)
-      DG_ADD(kDgEnqueue, t_e);
-      DG_CNT(kDgNEnqueue);
     };
     auto test_job = [&](int t, const f32x16& ac, auto UI) {
       constexpr int u = decltype(UI)::value;
-      if constexpr (GMAX) {
+      if constexpr (GMAX) {  // sample scan: the user tile's maxima only
         gmax_ut(t, ac, UI);
         return;
       }
@@ -1429,8 +1363,10 @@ __global__ __launch_bounds__(waves_for(W) * 64, waves_for(W) / 4) void score_sca
       const uint64_t bal = __ballot(hot(hot_max16(ac), thr[u]));
       DG_ADD(kDgHits, t_h);
       if (bal == 0ull) return;
-      if constexpr (STAGED) stage_ut(t, ac, bal, UI);
-      else enqueue_ut(t, ac, UI);
+      DG_T0(t_e);
+      stage_ut(t, ac, bal, UI);
+      DG_ADD(kDgEnqueue, t_e);
+      DG_CNT(kDgNEnqueue);
     };
     auto stage_end_utp = [&]() {
       if constexpr (STAGED) {
@@ -1547,12 +1483,11 @@ bool launch_scan_widths(const Plan& p, const TopkArgs& a, int w, bool seeded, hi
     if (done || w != WW) return;
     done = true;
 #define DR_SCAN(CC, SD) \
-  hipLaunchKernelGGL((score_scan_kernel<WW, CC, SD, F32>), dim3(p.grid), dim3(waves_for(WW) * 64), \
+  hipLaunchKernelGGL((score_scan_kernel<WW, CC, SD, F32>), dim3(p.grid), dim3(kWavesScan * 64), \
                      0, s, a)
 #define DR_SCAN_GMAX(CC) \
   hipLaunchKernelGGL((score_scan_kernel<WW, CC, false, F32, true>), dim3(p.grid),               \
-                     dim3(waves_for(WW) * 64),                                               \
-                     0, s, a)
+                     dim3(kWavesScan * 64), 0, s, a)
     if (a.gmax && !seeded) {  // sample scans (ks <= ~70 keys: CAP 512, or 1024 at narrow rows)
       if (p.cap == 512) DR_SCAN_GMAX(512);
       else if (p.cap == 1024) DR_SCAN_GMAX(1024);

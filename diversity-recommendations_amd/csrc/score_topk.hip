@@ -548,7 +548,7 @@ Plan make_plan(int64_t n_users, int64_t n_items, int w, int k, bool seedable,
     p.all_keys = n_items;
     while (p.cap < n_items) p.cap <<= 1;
   }
-  p.users_per_wg = nut_for(w) * 32 * waves_for(w);
+  p.users_per_wg = nut_for(w) * 32 * kWavesScan;
   p.n_ublocks = dr::ceil_div(n_users, p.users_per_wg);
   p.n_users_pad = p.n_ublocks * p.users_per_wg;
   const int64_t slots = device_cus();
@@ -744,7 +744,7 @@ Guess guess_for(int64_t n_items, int k, bool split_tail) {
 
 size_t diag_bytes() {
 #ifdef DR_TOPK_DIAG
-  return (size_t)device_cus() * kMaxWaves * kDgSlots * sizeof(uint64_t);
+  return (size_t)device_cus() * kWavesScan * kDgSlots * sizeof(uint64_t);
 #else
   return 0;
 #endif
