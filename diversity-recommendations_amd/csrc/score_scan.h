@@ -75,7 +75,10 @@ enum {
 // removed (DESIGN.md §3.1, A/B records under profiles/): one wave per SIMD
 // (rounds 2 and 5), 12 / 16 waves at d <= 64, SIMD-pair priorities, two
 // accumulator sets in ping-pong, the A fragments read per half chain, other
-// stage sizes, slacks and flush gaps. The one -D knob kept is the d = 128
+// stage sizes, slacks and flush gaps; in the direct survivor path
+// (enqueue_ut, profiles/survivor_regs/) per-user key counts in registers
+// instead of the LDS atomic, and v_xad_u32 for the A-fragment addresses.
+// The one -D knob kept is the d = 128
 // stage size (DR_STAGE_BYTES_WIDE, tools/build_variants.sh), re-measured in
 // round 6 with PMC FETCH beside the time at the headline (1M x 10M, k = 100;
 // profiles/r06/stage_fetch/): 72 KB 1770 ms, main-scan FETCH 227.6 GB;
@@ -963,64 +966,83 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
       return any;
     };
 
-    // Append survivors straight to their users' candidate buffers in HBM: one
-    // key per lane per round, its slot from the user's LDS key counter. No
-    // call and no queue in the hot loop, so nothing forces the accumulators
-    // and B fragments out of registers. A stage adds at most MARGIN keys per
-    // user, so a buffer compacted at the stage end never overflows.
-    // enqueue_ut is one user tile u of the group. gbase (the item tile's first
-    // item id) and vmask (valid_rows) belong to the item tile and are passed
-    // in: recomputed per user tile they took the d = 128 CAP 512 / 1024 scans
-    // from 12-13 spilled VGPRs and 64 B of scratch to 20 and 96 B.
-    auto enqueue_ut = [&](const f32x16& ac, auto UI, uint32_t gbase, uint32_t vmask) {
+    // Append survivors straight to their users' candidate buffers in HBM, each
+    // key's slot from the user's LDS key counter. No call and no queue in the
+    // hot loop, so nothing forces the accumulators and B fragments out of
+    // registers. A stage adds at most MARGIN keys per user, so a buffer
+    // compacted at the stage end never overflows.
+    // enqueue_ut is one user tile u of the group: one block per score register
+    // r. m[r], the ballot of `score r > threshold`, is the v_cmp's own SGPR
+    // pair; with only its lanes active the block takes the slot, builds the key
+    // of the compile-time row score_row(r, h) and stores it. A lane with
+    // several survivors takes part in several blocks; no per-lane mask, no
+    // 16-way value select, no second max. Almost always ONE block of the 16
+    // has a lane (a hit every 6th tile at the headline, one key), so what this
+    // costs is the scalar branches that skip the empty ones: a binary tree
+    // over the ORs of m[] reaches the block in 8 tests, 4 of them taken.
+    // Measured at 1M x 10M, k = 100 against the per-lane mask and loop this
+    // replaced (profiles/survivor_regs/): sixteen blocks each behind its own
+    // test 0.0 %, skipped in groups of four -0.6 %, the tree -0.9 % (-3.9 %
+    // at 1.25M rows).
+    // vmc is bumped under wave-uniform branches only and stays in an SGPR.
+    // gbase_h (the item id of the lane's score register 0) belongs to the item
+    // tile and is passed in, as the partial-tile rule is applied there.
+    auto enqueue_ut = [&](const f32x16& ac, auto UI, uint32_t gbase_h) {
       constexpr int u = decltype(UI)::value;
-      uint32_t mask = 0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mask |= (ac[r] > thr[u] ? 1u : 0u) << r;
-      mask &= vmask;
       const int slot = u * 32 + col;
       uint64_t* ubuf = cbase + (size_t)slot * CAP;  // this lane's user buffer
-      // Common case: every hitting lane holds ONE survivor. It is then the
-      // lane's maximum (all other scores are <= thr < it), so one round
-      // stores it without the 16-way value select. Full tiles only (the
-      // max of a partial tile may sit in a row past the slice end).
-      if (vmask == 0xffffu && __ballot((mask & (mask - 1u)) != 0u) == 0ull) {
-        if (__ballot(mask != 0u) != 0ull) {
-          float m = max16(ac);
-          if (mask != 0u) {
-            const int row = score_row(__builtin_ctz(mask), h);
-            const uint32_t pos = atomicAdd(&ucnt[slot], 1u);
-            if (pos < (uint32_t)CAP) st64(ubuf + pos, dr::make_key(m, gbase + (uint32_t)row));
-          }
-          vmc += 1;  // the store above issued once (some lane had a key)
-        }
-        return;
-      }
-      while (__ballot(mask != 0u) != 0ull) {
-        const bool has = mask != 0u;
-        const int r = has ? __builtin_ctz(mask) : 0;
-        mask &= mask - 1u;
-        float v = ac[0];
+      uint64_t m[16];
 #pragma unroll
-        for (int q = 1; q < 16; ++q) v = (r == q) ? ac[q] : v;
-        const int row = score_row(r, h);
-        if (has) {
+      for (int r = 0; r < 16; ++r) m[r] = __ballot(ac[r] > thr[u]);  // strict: never a NaN score
+      auto block = [&](auto RI) {
+        constexpr int r = decltype(RI)::value;
+        if (m[r] == 0ull) return;
+        if (__builtin_amdgcn_inverse_ballot_w64(m[r])) {
           const uint32_t pos = atomicAdd(&ucnt[slot], 1u);
           if (pos < (uint32_t)CAP)  // always true (flush_at + MARGIN <= CAP): a guard only
-            st64(ubuf + pos, dr::make_key(v, gbase + (uint32_t)row));
+            st64(ubuf + pos, dr::make_key(ac[r], gbase_h + (uint32_t)score_row(r, 0)));
         }
         vmc += 1;  // the store above issued once (some lane had a key)
-      }
+      };
+      // blocks [r0, r0 + n): skipped together when none of them has a lane
+      auto blocks = [&](auto& self, auto R0, auto N) {
+        constexpr int r0 = decltype(R0)::value, n = decltype(N)::value;
+        if constexpr (n == 1) {
+          block(R0);
+        } else {
+          uint64_t any = 0ull;
+#pragma unroll
+          for (int r = r0; r < r0 + n; ++r) any |= m[r];
+          if (any != 0ull) {
+            self(self, IC<r0>{}, IC<n / 2>{});
+            self(self, IC<r0 + n / 2>{}, IC<n / 2>{});
+          }
+        }
+      };
+      blocks(blocks, IC<0>{}, IC<8>{});
+      blocks(blocks, IC<8>{}, IC<8>{});
     };
     auto enqueue = [&](int t, f32x16 (&acc)[NG], const uint64_t (&hb)[NG], auto GI) {
       constexpr int g0 = decltype(GI)::value * NG;
       DG_T0(t_e);
       const int64_t tile0 = i_beg + (int64_t)t * kTileItems;
-      const uint32_t gbase = (uint32_t)(a.item_base + tile0);
-      const uint32_t vmask = valid_rows(i_end - tile0, h);
+      // score_row(r, h) = score_row(r, 0) + 4 h
+      const uint32_t gbase_h = (uint32_t)(a.item_base + tile0) + 4u * (uint32_t)h;
+      // The slice's last tile (a wave-uniform test, true once per unit): the
+      // scores of rows past the slice end become -inf, which no threshold
+      // admits. A full tile pays the scalar branch; the blocks pay nothing
+      // (the validity bit ANDed into m[r] behind a test in each block put 16
+      // more taken branches on every hit: +3.7 % at the headline).
+      if (i_end - tile0 < kTileItems) {
+        const uint32_t vmask = valid_rows(i_end - tile0, h);
+#pragma unroll
+        for (int j = 0; j < NG; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[j][r] = ((vmask >> r) & 1u) ? acc[j][r] : -INFINITY;
+      }
       static_for<0, NG>([&](auto J) {
         constexpr int j = decltype(J)::value;
-        if (hb[j] != 0ull) enqueue_ut(acc[j], IC<g0 + j>{}, gbase, vmask);
+        if (hb[j] != 0ull) enqueue_ut(acc[j], IC<g0 + j>{}, gbase_h);
       });
       DG_ADD(kDgEnqueue, t_e);
       DG_CNT(kDgNEnqueue);
