@@ -31,7 +31,9 @@ using namespace dr_topk;
 // Where a user's candidate buffers live (Plan / TopkArgs): every user has its
 // chunk-0 buffer at row = its position; a user of a split tail block has
 // chunks - 1 more at rows n_users_pad + (j - 1) * tail_pad + (u - head_users).
-constexpr int kMaxChunks = 16;  // = kMaxTailChunks (the plan's bound)
+// kMaxTailChunks: the most buffers a user has (the planner's bound on a tail
+// block's chunks, and the static bound of gather_candidates' unrolled loop).
+constexpr int kMaxTailChunks = 16;
 
 struct BufMap {
   int64_t n_users_pad;
@@ -47,6 +49,72 @@ struct BufMap {
 BufMap buf_map(const Plan& p) {
   return BufMap{p.n_users_pad, p.head_users(), (p.n_ublocks - p.n_head) * p.users_per_wg,
                 p.tail_chunks};
+}
+
+// Drop the keys of excluded items (sorted exclusion list of n items):
+// lower_bound of every key's item by binary lifting, one runtime loop over the
+// (uniform) steps around the unrolled per-key work, so key[] keeps static
+// indices (P independent searches, each a loop of its own, left key[] in
+// scratch at P >= 16).
+template <int P>
+__device__ __forceinline__ void drop_excluded(uint64_t (&key)[P], const int32_t* __restrict__ list,
+                                              int n) {
+  if (n <= 0) return;
+  int lo[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) lo[i] = 0;
+  int step = 1;
+  while (2 * step <= n) step *= 2;
+  for (; step > 0; step >>= 1) {
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      const int c = lo[i] + step;
+      if (c <= n && list[c - 1] < (int32_t)dr::key_item(key[i])) lo[i] = c;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < P; ++i)
+    if (key[i] != 0ull && lo[i] < n && list[lo[i]] == (int32_t)dr::key_item(key[i])) key[i] = 0ull;
+}
+
+// The k best of a sorted key array (element e = lane*P + i) to output row
+// `row`, decoded; empty slots (key 0) as score -inf, item -1.
+template <int P>
+__device__ __forceinline__ void write_best(const uint64_t (&key)[P], int k,
+                                           float* __restrict__ out_s, int32_t* __restrict__ out_i,
+                                           int64_t row) {
+  const int lane = dr::lane_id();
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    const int e = lane * P + i;
+    if (e < k) {
+      const bool empty = key[i] == 0ull;
+      out_s[row * k + e] = empty ? -INFINITY : dr::key_score(key[i]);
+      out_i[row * k + e] = empty ? -1 : (int32_t)dr::key_item(key[i]);
+    }
+  }
+}
+
+// A threshold strictly below score s, so that every score >= s passes the
+// scan's `score > thr` test; -inf (no pruning) for NaN and infinite scores.
+__device__ __forceinline__ float below_score(float s) {
+  const float b = s - fmaxf(fabsf(s) * 0x1p-20f, 0x1p-100f);
+  return b < s ? b : -INFINITY;
+}
+
+// The best 1024 of `total` streamed keys, sorted, in elements [0, 1024) of a
+// 2048-key register array: load(x0, lane0) puts the keys at stream positions
+// x0 + (lane - lane0) * 32 + i into key[i] of the lanes >= lane0 (0 past the
+// end). Every round re-sorts the running best with the next 1024 keys, which
+// enter elements [1024, 2048).
+template <typename Load>
+__device__ __forceinline__ void stream_best_1024(uint64_t (&key)[32], int64_t total, Load load) {
+  load(0, 0);
+  dr::wave_sort_desc<32>(key);
+  for (int64_t next = 64 * 32; next < total; next += 32 * 32) {
+    load(next, 32);
+    dr::wave_sort_desc<32>(key);
+  }
 }
 
 // One user's candidate keys of every buffer into registers (element e =
@@ -66,7 +134,7 @@ __device__ __forceinline__ void gather_candidates(const uint64_t* __restrict__ c
   int off = 0;
   // chunk loop unrolled to its static bound so key[] stays in registers
 #pragma unroll
-  for (int c = 0; c < kMaxChunks; ++c) {
+  for (int c = 0; c < kMaxTailChunks; ++c) {
     if (c < nc) {
       const int64_t r = m.row(u, c);
       const int n = cnt[r];
@@ -81,30 +149,7 @@ __device__ __forceinline__ void gather_candidates(const uint64_t* __restrict__ c
   }
   if (excl_rowptr) {  // er: the user's exclusion row
     const int64_t e0 = excl_rowptr[er], e1 = excl_rowptr[er + 1];
-    const int n = (int)(e1 - e0);
-    const int32_t* list = excl_items + e0;
-    if (n > 0) {
-      // lower_bound of every key's item by binary lifting: one runtime loop
-      // over the (uniform) steps around the unrolled per-key work, so key[]
-      // keeps static indices (P independent searches, each a loop of its
-      // own, left key[] in scratch at P >= 16)
-      int lo[P];
-#pragma unroll
-      for (int i = 0; i < P; ++i) lo[i] = 0;
-      int step = 1;
-      while (2 * step <= n) step *= 2;
-      for (; step > 0; step >>= 1) {
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-          const int c = lo[i] + step;
-          if (c <= n && list[c - 1] < (int32_t)dr::key_item(key[i])) lo[i] = c;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < P; ++i)
-        if (key[i] != 0ull && lo[i] < n && list[lo[i]] == (int32_t)dr::key_item(key[i]))
-          key[i] = 0ull;
-    }
+    drop_excluded<P>(key, excl_items + e0, (int)(e1 - e0));
   }
 }
 
@@ -137,44 +182,13 @@ __global__ __launch_bounds__(256) void topk_finalize_kernel(
   uint64_t key[P];
   gather_candidates<P>(cand, cnt, m, cap, u, excl_rowptr, excl_items, op, key);
   dr::wave_sort_desc<P>(key);
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    const int e = lane * P + i;
-    if (e < k) {
-      const bool empty = key[i] == 0ull;
-      out_s[op * k + e] = empty ? -INFINITY : dr::key_score(key[i]);
-      out_i[op * k + e] = empty ? -1 : (int32_t)dr::key_item(key[i]);
-    }
-  }
+  write_best<P>(key, k, out_s, out_i, op);
   if (fail_cnt && lane == (k - 1) / P && dr::select_key<P>(key, (k - 1) % P) == 0ull) {
     const int32_t f = atomicAdd(fail_cnt, 1);
     fail_rows[f] = user_ids ? user_ids[u] : u;
     fail_pos[f] = op;
     if (fail_thr) fail_thr[f] = fail_thr_src[u];  // the user's second-tier threshold
   }
-}
-
-// Drop the keys of excluded items (sorted exclusion list of n items): binary
-// lifting in one uniform loop over the steps, so key[] keeps static indices.
-template <int P>
-__device__ __forceinline__ void drop_excluded(uint64_t (&key)[P], const int32_t* __restrict__ list,
-                                              int n) {
-  if (n <= 0) return;
-  int lo[P];
-#pragma unroll
-  for (int i = 0; i < P; ++i) lo[i] = 0;
-  int step = 1;
-  while (2 * step <= n) step *= 2;
-  for (; step > 0; step >>= 1) {
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-      const int c = lo[i] + step;
-      if (c <= n && list[c - 1] < (int32_t)dr::key_item(key[i])) lo[i] = c;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < P; ++i)
-    if (key[i] != 0ull && lo[i] < n && list[lo[i]] == (int32_t)dr::key_item(key[i])) key[i] = 0ull;
 }
 
 // ------------------------------------------------------------------ second-tier finalize
@@ -242,21 +256,8 @@ __global__ __launch_bounds__(256) void topk_finalize_stream_kernel(
 #pragma unroll
     for (int i = 0; i < P; ++i) key[i] = nk[i];
   };
-  load(0, 0);
-  dr::wave_sort_desc<P>(key);
-  for (int64_t next = 64 * P; next < total; next += 32 * P) {
-    load(next, 32);
-    dr::wave_sort_desc<P>(key);
-  }
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    const int e = lane * P + i;
-    if (e < k) {
-      const bool empty = key[i] == 0ull;
-      out_s[op * k + e] = empty ? -INFINITY : dr::key_score(key[i]);
-      out_i[op * k + e] = empty ? -1 : (int32_t)dr::key_item(key[i]);
-    }
-  }
+  stream_best_1024(key, total, load);
+  write_best<P>(key, k, out_s, out_i, op);
   if (lane == (k - 1) / P && dr::select_key<P>(key, (k - 1) % P) == 0ull) {
     const int32_t f = atomicAdd(fail_cnt, 1);
     fail_rows[f] = user_ids[u];
@@ -291,14 +292,8 @@ __global__ __launch_bounds__(256) void topk_threshold_kernel(
   uint64_t key[P];
   gather_candidates<P>(cand, cnt, m, cap, u, nullptr, nullptr, u, key);
   dr::wave_sort_desc<P>(key);
-  auto below_key = [](uint64_t kk) {
-    float t = -INFINITY;
-    if (kk != 0ull) {
-      const float s = dr::key_score(kk);
-      const float below = s - fmaxf(fabsf(s) * 0x1p-20f, 0x1p-100f);
-      t = below < s ? below : -INFINITY;  // NaN / inf scores: no pruning
-    }
-    return t;
+  auto below_key = [](uint64_t kk) {  // an empty slot: fewer than that many candidates
+    return kk != 0ull ? below_score(dr::key_score(kk)) : -INFINITY;
   };
   if (lane == (k1 - 1) / P) thr[u] = below_key(dr::select_key<P>(key, (k1 - 1) % P));
   if (thr2 && lane == (k - 1) / P) thr2[u] = below_key(dr::select_key<P>(key, (k - 1) % P));
@@ -323,11 +318,6 @@ __global__ __launch_bounds__(256) void topk_threshold_kernel(
 constexpr int kDenseMaxKs = 72;
 constexpr int kDenseBuf = 24;
 constexpr double kDenseMaxGiB = 16.0;
-
-__device__ __forceinline__ float below_score(float s) {
-  const float b = s - fmaxf(fabsf(s) * 0x1p-20f, 0x1p-100f);
-  return b < s ? b : -INFINITY;  // -inf / +inf: no pruning
-}
 
 template <int KS>
 __global__ __launch_bounds__(256) void topk_threshold_dense_kernel(
@@ -397,18 +387,17 @@ __global__ __launch_bounds__(256) void topk_threshold_dense_kernel(
 bool launch_threshold_dense(const float* tmax, int64_t T, int64_t n_pad, int64_t n_users, int k,
                             int k1, float* thr, float* thr2, hipStream_t s) {
   const dim3 grid((unsigned)dr::ceil_div(n_pad, 256));
-#define DR_TD(KK) \
-  hipLaunchKernelGGL((topk_threshold_dense_kernel<KK>), grid, dim3(256), 0, s, tmax, T, n_pad, \
-                     n_users, k, k1, thr, thr2)
-  if (k <= 8) DR_TD(8);
-  else if (k <= 16) DR_TD(16);
-  else if (k <= 24) DR_TD(24);
-  else if (k <= 32) DR_TD(32);
-  else if (k <= 48) DR_TD(48);
-  else if (k <= 72) DR_TD(72);
-  else return false;
-#undef DR_TD
-  return true;
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, tmax, T, n_pad, n_users, k, k1, thr, thr2);
+    return true;
+  };
+  if (k <= 8) return go(topk_threshold_dense_kernel<8>);
+  if (k <= 16) return go(topk_threshold_dense_kernel<16>);
+  if (k <= 24) return go(topk_threshold_dense_kernel<24>);
+  if (k <= 32) return go(topk_threshold_dense_kernel<32>);
+  if (k <= 48) return go(topk_threshold_dense_kernel<48>);
+  if (k <= 72) return go(topk_threshold_dense_kernel<72>);
+  return false;
 }
 
 // ------------------------------------------------------------------ merge
@@ -437,15 +426,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     key[i] = kk;
   }
   dr::wave_sort_desc<P>(key);
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    const int e = lane * P + i;
-    if (e < k_out) {
-      const bool empty = key[i] == 0ull;
-      out_s[u * k_out + e] = empty ? -INFINITY : dr::key_score(key[i]);
-      out_i[u * k_out + e] = empty ? -1 : (int32_t)dr::key_item(key[i]);
-    }
-  }
+  write_best<P>(key, k_out, out_s, out_i, u);
 }
 
 int p_for(int total) {
@@ -459,6 +440,8 @@ int p_for(int total) {
 // Workgroup slots = CUs (one 512-thread workgroup per CU). DR_KNOB_SCAN_SLOTS
 // overrides the count so that tests can reach the split-tail plans with
 // small inputs; the result is identical for any plan.
+size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 int knob_int(int id, int fallback) {
   double v;
   return dr::plan_knob(id, &v) ? (int)v : fallback;
@@ -486,19 +469,14 @@ int cap_for(int w, int k) {
   return -1;
 }
 
-constexpr int kMaxTailChunks = 16;
-constexpr bool kLongFlush = true;  // long lists flush at CAP - margin, not k + kSlack + kFlushGap
 // Compaction slack and flush gap of the sample scan (ks <= ~70 keys per user).
-constexpr int kSampleSlackDefault = 32;
-constexpr int kSampleGapDefault = 96;
+constexpr int kSampleSlack = 32;
+constexpr int kSampleGap = 96;
 constexpr int kSampleGmax = 1;  // sample scans keep tile maxima (TopkArgs::gmax)
-constexpr int kSampleSlack = kSampleSlackDefault;
-constexpr int kSampleGap = kSampleGapDefault;
 // The finalize of a split-tail user sorts every chunk's end-compacted keys
 // (<= k + kSlack each) in one wave; at most 1024 of them keeps its sort at
 // P = 16 (a 2048-key sort costs ~6x the 512-key one of a whole-catalog user).
 constexpr int kMaxTailKeys = 1024;
-constexpr bool kHeadKeep = true;  // long lists: whole-catalog units end compacted to 1024 keys
 
 // Grid tail: U users make B = ceil(U / UPWG) user blocks for `slots`
 // workgroups. Whole-catalog units run in ceil(B / slots) rounds, the last one
@@ -534,7 +512,6 @@ constexpr bool kHeadKeep = true;  // long lists: whole-catalog units end compact
 // chunk compacts; the finalize gathers every chunk's keys): 943 x 1682 d = 64
 // 1.55 -> 0.86 ms, 10K x 2000 k = 100 2.05 -> 1.10, config 1's step 3.17 ->
 // 2.43 ms. Unseeded main scans only (the caller says so: allow_keep_all).
-constexpr bool kKeepAll = true;
 constexpr int64_t kKeepAllItems = 2048;
 constexpr int64_t kKeepAllUsers = 16384;
 
@@ -542,7 +519,7 @@ Plan make_plan(int64_t n_users, int64_t n_items, int w, int k, bool seedable,
                bool allow_keep_all = false) {
   Plan p{};
   p.cap = cap_for(w, k);
-  if (kKeepAll && allow_keep_all && !seedable && p.cap > 0 && n_items <= kKeepAllItems &&
+  if (allow_keep_all && !seedable && p.cap > 0 && n_items <= kKeepAllItems &&
       n_users <= kKeepAllUsers && w <= 256) {  // CAP-2048 instances exist for w <= 256
     p.keep_all = 1;
     p.all_keys = n_items;
@@ -599,8 +576,7 @@ Plan make_plan(int64_t n_users, int64_t n_items, int w, int k, bool seedable,
   // survivors (the guess's rank): with the flush at k + 128 = 1128 every user
   // compacted a ~1.1K-key buffer 3-4 times in the last third of the catalog;
   // at CAP - margin = 1792 most users never compact.
-  p.gap = head_flush > kMaxTailKeys && kLongFlush ? p.cap - (int)stage_items - k - kSlack
-                                                     : kFlushGap;
+  p.gap = head_flush > kMaxTailKeys ? p.cap - (int)stage_items - k - kSlack : kFlushGap;
   // a tail chunk ends with at most end_keep >= k keys, so c of them fit the
   // finalize's max_keys
   p.end_keep = best_c > 1 && !p.keep_all ? std::min(k + kSlack, max_keys / best_c) : 0;
@@ -608,12 +584,12 @@ Plan make_plan(int64_t n_users, int64_t n_items, int w, int k, bool seedable,
   // with a compaction to at most kMaxTailKeys keys (slack kMaxTailKeys - k), so
   // the finalize sorts 1024 keys per user instead of 2048 (k = 1000: the
   // 2048-key sort cost ~24 ms per 1M users).
-  p.head_keep = kHeadKeep && head_flush > kMaxTailKeys && k + 8 <= kMaxTailKeys ? kMaxTailKeys : 0;
+  p.head_keep = head_flush > kMaxTailKeys && k + 8 <= kMaxTailKeys ? kMaxTailKeys : 0;
   p.buf_rows = p.n_users_pad + (int64_t)(best_c - 1) * (B - p.n_head) * p.users_per_wg;
   const int64_t units = p.n_head + (B - p.n_head) * best_c;
   p.grid = (int)(units < slots ? units : slots);
   p.cand_bytes = (size_t)p.buf_rows * p.cap * sizeof(uint64_t);
-  p.cnt_bytes = ((size_t)p.buf_rows * sizeof(int32_t) + 255) & ~(size_t)255;
+  p.cnt_bytes = al256((size_t)p.buf_rows * sizeof(int32_t));
   return p;
 }
 
@@ -642,8 +618,9 @@ int tail_keys(const Plan& p, int w, int k) {
   return n > 256 ? n : 256;
 }
 
-// Guessed thresholds (kGuess). A scan that starts at -inf stores every
-// running top-k record of a user: ~k * (1 + ln(I / k)) keys, the survivor
+// Guessed thresholds, for catalogs of >= kGuessMinItems rows. A scan that
+// starts at -inf stores every running top-k record of a user:
+// ~k * (1 + ln(I / k)) keys, the survivor
 // stream that dominates short catalogs (47 % of wave time at d=64 over 1M
 // items). Instead a first scan over a strided sample of S = I / kGuessStride
 // rows keeps each user's ks best, and the main scan starts from just below the
@@ -665,9 +642,7 @@ struct Guess {
   int ks1 = 0;         // first-tier rank (<= ks): the main scan's threshold
 };
 
-constexpr bool kGuess = true;  // guessed thresholds for catalogs of >= 2^18 rows
 constexpr double kGuessSigma = 6.0;
-constexpr int kGuessStrideDefault = 32;
 // Two-tier guess (round 3): the main scan starts from the sample's
 // ks1-th best score; the users it fails are rescanned from their safe
 // (6-sigma) threshold by a second-tier scan spread over every CU, and the
@@ -694,10 +669,9 @@ constexpr double kGuessTail = 0.005;
 // rescan 6.8 -> ~3.9 ms, call -2.9 ms; k = 1000 -1.9 ms; lists identical,
 // profiles/r06/rescan_chunks/)
 constexpr int kMaxRescanChunks = 128;
-constexpr int64_t kGuessStride = kGuessStrideDefault;
+constexpr int64_t kGuessStride = 32;
 constexpr int64_t kGuessMinItems = 1 << 18;
-constexpr int kGuessMaxLog2 = 23;  // measured: +1.7 % at 5M rows, -0.3 % at 10M
-constexpr int64_t kGuessMaxItems = 1ll << kGuessMaxLog2;
+constexpr int64_t kGuessMaxItems = 1ll << 23;  // measured: +1.7 % at 5M rows, -0.3 % at 10M
 // Long lists pay a survivor stream of ~k (1 + ln(I / k)) keys per user from
 // -inf (10K keys at k = 1000 over 10M items: 3.5x the k = 100 scan), which the
 // guess removes at any catalog length.
@@ -708,7 +682,7 @@ constexpr int kGuessLongK = 256;
 // ~c times the keys of one whole-catalog pass for its users.
 Guess guess_for(int64_t n_items, int k, bool split_tail) {
   Guess g;
-  if (!kGuess || n_items < kGuessMinItems) return g;
+  if (n_items < kGuessMinItems) return g;
   const int force = knob_int(DR_KNOB_SCAN_SEED, -1);  // A/B knob: 0 never, 1 always
   if (force == 0) return g;
   if (n_items > kGuessMaxItems && k < kGuessLongK && !split_tail && force != 1) return g;
@@ -750,8 +724,6 @@ size_t diag_bytes() {
 #endif
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Workspace layout, 256-B aligned pieces:
 //   [cand | cnt | thr (tier 1, tier 2) | sample rows | fail rows | fail positions |
 //    fail thresholds | tier-2 fail rows | tier-2 fail positions | fail counts | diag].
@@ -773,10 +745,35 @@ size_t dense_bytes(int64_t n_users_pad, int64_t S) {
   return (size_t)n_users_pad * (size_t)(S / kTileItems) * 4;
 }
 
+// The sample scan of the guessed thresholds, as dr_score_topk and
+// dr_sample_thresholds both run it: S tile-transposed sample rows scanned from
+// -inf for each user's ks best tile maxima.
+struct SampleScan {
+  Plan plan{};         // over the S rows at rank ks, compacted tighter (kSampleSlack / kSampleGap)
+  int64_t S = 0;       // sample rows, whole tiles (0: no sample)
+  int ks = 0;
+  bool dense = false;  // dense tile maxima (gmax == 2) instead of the compaction path
+  size_t cand_bytes = 0;  // what the scan needs of the candidate region
+  int64_t tiles() const { return S / kTileItems; }
+};
+
+SampleScan sample_scan_for(int64_t n_users, int64_t S, int w, int ks) {
+  SampleScan ss;
+  ss.S = S;
+  ss.ks = ks;
+  if (S == 0) return ss;
+  ss.plan = make_plan(n_users, S, w, ks, false);
+  ss.plan.slack = kSampleSlack;
+  ss.plan.gap = kSampleGap;
+  ss.dense = sample_dense(ks, ss.plan.n_users_pad, S);
+  ss.cand_bytes = ss.dense ? al256(dense_bytes(ss.plan.n_users_pad, S)) : ss.plan.cand_bytes;
+  return ss;
+}
+
 struct Layout {
-  Plan main, sample;
+  Plan main;
+  SampleScan sample;
   Guess g;
-  bool dense = false;  // the sample scan keeps dense tile maxima
   size_t cand = 0, cnt = 0, thr = 0, samp = 0, frows = 0, fpos = 0, fthr = 0, fcnt = 0, diag = 0;
   size_t off_thr() const { return cand + cnt; }
   size_t off_samp() const { return off_thr() + 2 * thr; }
@@ -792,19 +789,14 @@ struct Layout {
 
 Layout make_layout(int64_t n_users, int64_t n_items, int w, int k) {
   Layout L{};
-  L.main = make_plan(n_users, n_items, w, k, kGuess && n_items >= kGuessMinItems, true);
+  L.main = make_plan(n_users, n_items, w, k, n_items >= kGuessMinItems, true);
   L.g = guess_for(n_items, k, L.main.tail_chunks > 1);
   L.cand = L.main.cand_bytes;
   L.cnt = L.main.cnt_bytes;
   if (L.g.S > 0) {
-    L.sample = make_plan(n_users, L.g.S, w, L.g.ks, false);
-    // the sample keeps only ks keys per user: compact it tighter
-    L.sample.slack = kSampleSlack;
-    L.sample.gap = kSampleGap;
-    L.dense = sample_dense(L.g.ks, L.sample.n_users_pad, L.g.S);
-    const size_t sb = L.dense ? al256(dense_bytes(L.sample.n_users_pad, L.g.S)) : L.sample.cand_bytes;
-    L.cand = L.cand > sb ? L.cand : sb;
-    L.cnt = L.cnt > L.sample.cnt_bytes ? L.cnt : L.sample.cnt_bytes;
+    L.sample = sample_scan_for(n_users, L.g.S, w, L.g.ks);
+    L.cand = std::max(L.cand, L.sample.cand_bytes);
+    L.cnt = std::max(L.cnt, L.sample.plan.cnt_bytes);
     L.thr = al256((size_t)L.main.n_users_pad * sizeof(float));
     L.samp = al256((size_t)L.g.S * w * 2);
     L.frows = al256((size_t)n_users * sizeof(int64_t));
@@ -821,7 +813,8 @@ Layout make_layout(int64_t n_users, int64_t n_items, int w, int k) {
 // row p = 32 r + q. A tile (the GMAX sample scan keeps one max per user and
 // tile) then holds samples T apart — catalog rows T * stride apart — so items
 // that cluster by id (e.g. ids ordered by popularity) fall into different
-// tiles. 16 B per thread.
+// tiles. dr_sample_thresholds' caller gathered its sample already: stride 1.
+// 16 B per thread.
 __global__ __launch_bounds__(256) void sample_rows_kernel(const uint4* __restrict__ I,
                                                           int64_t stride, int64_t S, int cpr,
                                                           uint4* __restrict__ out) {
@@ -848,6 +841,234 @@ bool launch_scan(const Plan& p, const TopkArgs& a, int dtype, int w, bool seeded
                          : launch_scan_bf16(p, a, w, seeded, s);
 }
 
+// ------------------------------------------------------------------ host-side launch sequence
+// The entry points below are written out of these steps. Each takes the entry
+// point's name `fn` for its error text and returns a DR_* code.
+#define DR_TRY(expr)                   \
+  do {                                 \
+    const int rc_ = (expr);            \
+    if (rc_ != DR_OK) return rc_;      \
+  } while (0)
+
+int arg_error(const char* fn, const char* msg) {
+  dr::set_error(std::string(fn) + ": " + msg);
+  return DR_EINVAL;
+}
+int plan_error(const char* fn, const char* what) {
+  dr::set_error(std::string(fn) + ": internal plan error (" + what + ")");
+  return DR_EUNSUPPORTED;
+}
+int launch_status(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return DR_OK;
+  dr::set_error(std::string(fn) + ": hipGetLastError() -> " + hipGetErrorString(e));
+  return DR_EHIP;
+}
+
+// The argument checks of dr_score_topk and dr_score_topk_seeded (thr_ok: the
+// seeded call's threshold pointer is set); *w = the row width. DR_OK with
+// n_users == 0 means "nothing to do": the pointers are not looked at then.
+int check_score_call(const char* fn, const void* user_table, int64_t n_users,
+                     const void* item_table, int64_t n_items, int64_t item_base, int dtype, int d,
+                     int k, const int64_t* excl_rowptr, const int32_t* excl_items,
+                     const float* out_scores, const int32_t* out_items, bool thr_ok, int* w) {
+  if (!(n_users >= 0 && n_items >= 0)) return arg_error(fn, "negative size");
+  if (!(k >= 1 && k <= 1024)) return arg_error(fn, "k must be in [1, 1024]");
+  if (!(dtype == DR_BF16 || dtype == DR_F32))
+    return arg_error(fn, "tables must be DR_BF16 or DR_F32");
+  *w = width_for(dtype, d);
+  if (!(*w > 0))
+    return arg_error(fn, dtype == DR_BF16 ? "bf16 d must be one of 32, 64, 128, 256, 512"
+                                          : "fp32 d must be one of 32, 64, 128, 256");
+  if (!(cap_for(*w, k) > 0)) return arg_error(fn, "k too large for this d");
+  if (!(item_base >= 0 && item_base + n_items < 0x7fffffffLL))
+    return arg_error(fn, "global item ids must fit int32");
+  if ((excl_rowptr == nullptr) != (excl_items == nullptr))
+    return arg_error(fn, "excl_rowptr and excl_items must both be set or both be NULL");
+  if (n_users == 0) return DR_OK;
+  if (!(user_table && out_scores && out_items && thr_ok)) return arg_error(fn, "null pointer");
+  if (n_items == 0) return arg_error(fn, "empty catalog");
+  if (!item_table) return arg_error(fn, "null item_table");
+  return DR_OK;
+}
+
+// The 256-B aligned base of the caller's workspace; NULL (error set; the
+// caller returns DR_EWORKSPACE) when fewer than `need` bytes follow it.
+char* workspace_base(const char* fn, void* workspace, size_t workspace_bytes, size_t need) {
+  char* ws = (char*)al256((uintptr_t)workspace);
+  if (workspace && (size_t)(ws - (char*)workspace) + need <= workspace_bytes) return ws;
+  dr::set_error(std::string(fn) + ": workspace too small (need " + std::to_string(need + 256) +
+                " bytes)");
+  return nullptr;
+}
+
+// TopkArgs of a scan under plan p: the plan's units and compaction bounds over
+// the caller's tables, with the candidate keys at ws and the counts cand_bytes
+// after them. Everything else is zero (item base 0, no exclusions, unseeded,
+// host-side user count, no diag block): the caller states what it changes.
+TopkArgs args_for(const Plan& p, const void* user_table, const int64_t* user_ids, int64_t n_users,
+                  const void* item_rows, int64_t n_items, int k, char* ws, size_t cand_bytes) {
+  TopkArgs a{};
+  a.U = (const char*)user_table;
+  a.user_ids = user_ids;
+  a.n_users = n_users;
+  a.n_users_pad = p.n_users_pad;
+  a.I = (const char*)item_rows;
+  a.n_items = n_items;
+  a.k = k;
+  a.n_ublocks = p.n_ublocks;
+  a.n_head = p.n_head;
+  a.tail_chunks = p.tail_chunks;
+  a.chunk_items = p.chunk_items;
+  a.end_keep = p.end_keep;
+  a.head_keep = p.head_keep;
+  a.slack = p.slack;
+  a.gap = p.gap;
+  a.keep_all = p.keep_all;
+  a.cand = (uint64_t*)ws;
+  a.cnt = (int32_t*)(ws + cand_bytes);
+  return a;
+}
+
+int run_scan(const char* fn, const Plan& p, const TopkArgs& a, int dtype, int w, bool seeded,
+             hipStream_t s) {
+  if (!launch_scan(p, a, dtype, w, seeded, s)) return plan_error(fn, "no scan instance");
+  return launch_status(fn);
+}
+
+// One finalize: which buffers, where the lists go, and (rescans) whose they
+// are; see topk_finalize_kernel.
+struct FinalizeArgs {
+  const uint64_t* cand;
+  const int32_t* cnt;
+  BufMap map;
+  int cap, k;
+  const int64_t* excl_rowptr;
+  const int32_t* excl_items;
+  float* out_s;
+  int32_t* out_i;
+  const int64_t* user_ids;               // the users' table rows (for the fail list)
+  const int64_t* pos_map = nullptr;      // rescans: list entry -> the caller's position
+  const int32_t* n_users_dev = nullptr;  // rescans: the list's length, on the device
+  // guessed scans: users left with fewer than k keys are appended here
+  int32_t* fail_cnt = nullptr;
+  int64_t* fail_rows = nullptr;
+  int64_t* fail_pos = nullptr;
+  const float* fail_thr_src = nullptr;  // [position] second-tier thresholds, copied to
+  float* fail_thr = nullptr;            // [fail list entry]
+};
+
+// Finalize users [u0, u1), one wave each, sorting at most `keys` keys per
+// user; false when no sort instance holds that many.
+bool launch_finalize(const FinalizeArgs& f, int64_t u0, int64_t u1, int keys, hipStream_t s) {
+  const dim3 grid((unsigned)dr::ceil_div(u1 - u0, 4));
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, f.cand, f.cnt, f.map, f.cap, u0, u1, f.k,
+                       f.excl_rowptr, f.excl_items, f.out_s, f.out_i, f.pos_map, f.n_users_dev,
+                       f.user_ids, f.fail_cnt, f.fail_rows, f.fail_pos, f.fail_thr_src, f.fail_thr);
+    return true;
+  };
+  switch (p_for(keys)) {
+    case 4: return go(topk_finalize_kernel<4>);
+    case 8: return go(topk_finalize_kernel<8>);
+    case 16: return go(topk_finalize_kernel<16>);
+    case 32: return go(topk_finalize_kernel<32>);
+    default: return false;
+  }
+}
+
+int finalize_range(const char* fn, const FinalizeArgs& f, int64_t u0, int64_t u1, int keys,
+                   hipStream_t s) {
+  if (u1 <= u0) return DR_OK;
+  if (!launch_finalize(f, u0, u1, keys, s)) return plan_error(fn, "candidate sort");
+  return launch_status(fn);
+}
+
+// Plan p's users: the head blocks' (one buffer each), then the split tail's
+// (their chunks' buffers), each range with the sort its key count needs.
+int finalize_head_and_tail(const char* fn, const FinalizeArgs& f, const Plan& p, int w,
+                           int64_t n_users, hipStream_t s) {
+  const int64_t head_end = std::min(p.head_users(), n_users);
+  DR_TRY(finalize_range(fn, f, 0, head_end, head_keys(p, w, f.k), s));
+  return finalize_range(fn, f, head_end, n_users, tail_keys(p, w, f.k), s);
+}
+
+// Thresholds of positions [u0, u1) from the compaction path's sample buffers
+// (topk_threshold_kernel); false when no sort instance holds `keys` keys.
+struct ThresholdArgs {
+  const uint64_t* cand;
+  const int32_t* cnt;
+  BufMap map;
+  int cap;
+  int64_t n_users;  // positions from here on are padding: +inf
+  int ks, ks1;      // ranks of thr2 (safe) and thr (first tier)
+  float* thr;
+  float* thr2;
+};
+
+bool launch_threshold(const ThresholdArgs& t, int64_t u0, int64_t u1, int keys, hipStream_t s) {
+  const dim3 grid((unsigned)dr::ceil_div(u1 - u0, 4));
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, t.cand, t.cnt, t.map, t.cap, u0, u1,
+                       t.n_users, t.ks, t.ks1, t.thr, t.thr2);
+    return true;
+  };
+  switch (p_for(keys)) {
+    case 4: return go(topk_threshold_kernel<4>);
+    case 8: return go(topk_threshold_kernel<8>);
+    case 16: return go(topk_threshold_kernel<16>);
+    case 32: return go(topk_threshold_kernel<32>);
+    default: return false;
+  }
+}
+
+// TopkArgs of the sample scan over `rows` (ss.S tile-transposed sample rows):
+// sample ids are sample rows, so no exclusions and no item base. The
+// candidate region starts at ws (the scan uses ss.cand_bytes of it: keys, or
+// the dense tile maxima), the counts cand_bytes after it.
+TopkArgs sample_args(const SampleScan& ss, const void* user_table, const int64_t* user_ids,
+                     int64_t n_users, const char* rows, char* ws, size_t cand_bytes) {
+  TopkArgs a = args_for(ss.plan, user_table, user_ids, n_users, rows, ss.S, ss.ks, ws, cand_bytes);
+  a.gmax = ss.dense ? 2 : kSampleGmax;
+  a.tmax = (float*)ws;
+  a.tmax_tiles = ss.tiles();
+  return a;
+}
+
+// The guess's first two steps: the sample scan (a = sample_args), then each
+// position's thresholds at sample ranks ks1 (thr) and ss.ks (thr2, may be
+// NULL), dense or by sorting the compaction path's buffers. Positions
+// [0, n_pos) are written; those from a.n_users on (padding) get +inf.
+int sample_scan_thresholds(const char* fn, const SampleScan& ss, const TopkArgs& a, int dtype,
+                           int w, int ks1, int64_t n_pos, float* thr, float* thr2,
+                           hipStream_t s) {
+  const Plan& p = ss.plan;
+  DR_TRY(run_scan(fn, p, a, dtype, w, false, s));
+  if (ss.dense) {
+    if (!launch_threshold_dense(a.tmax, a.tmax_tiles, n_pos, a.n_users, ss.ks, ks1, thr, thr2, s))
+      return plan_error(fn, "dense threshold rank");
+    return launch_status(fn);
+  }
+  const ThresholdArgs t{a.cand, a.cnt, buf_map(p), p.cap, a.n_users, ss.ks, ks1, thr, thr2};
+  const int64_t head_end = std::min(p.head_users(), n_pos);
+  auto range = [&](int64_t u0, int64_t u1, int keys) {
+    if (u1 <= u0) return (int)DR_OK;
+    if (!launch_threshold(t, u0, u1, keys, s)) return plan_error(fn, "candidate sort");
+    return launch_status(fn);
+  };
+  DR_TRY(range(0, head_end, head_keys(p, w, ss.ks)));
+  return range(head_end, n_pos, tail_keys(p, w, ss.ks));
+}
+
+// Tile-transposed copy of S sample rows (rows j * stride of `table`).
+int copy_sample_rows(const char* fn, const void* table, int64_t stride, int64_t S, int w,
+                     char* out, hipStream_t s) {
+  const int cpr = w / 8;  // 16-B chunks per row
+  hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)dr::ceil_div(S * cpr, 256)), dim3(256), 0,
+                     s, (const uint4*)table, stride, S, cpr, (uint4*)out);
+  return launch_status(fn);
+}
+
 // ------------------------------------------------------------------ streaming merge
 // Merge of more than 2048 partial entries per user (e.g. 8 shards x top-1000):
 // one wave per user keeps the running best keys in elements [0, 1024) of a
@@ -861,7 +1082,7 @@ __global__ __launch_bounds__(256) void topk_merge_stream_kernel(
   const int64_t u = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
   if (u >= n_users) return;  // wave-uniform
   const int64_t total = (int64_t)parts * k_in;
-  auto load = [&](int64_t e) -> uint64_t {
+  auto entry = [&](int64_t e) -> uint64_t {
     if (e >= total) return 0ull;
     const int64_t p = e / k_in, j = e % k_in;
     const size_t o = ((size_t)p * n_users + u) * k_in + j;
@@ -869,25 +1090,12 @@ __global__ __launch_bounds__(256) void topk_merge_stream_kernel(
     return it < 0 ? 0ull : dr::make_key(in_s[o], (uint32_t)it);
   };
   uint64_t key[P];
+  stream_best_1024(key, total, [&](int64_t x0, int lane0) {
+    if (lane < lane0) return;
 #pragma unroll
-  for (int i = 0; i < P; ++i) key[i] = load((int64_t)lane * P + i);
-  dr::wave_sort_desc<P>(key);
-  for (int64_t next = 64 * P; next < total; next += 32 * P) {
-    if (lane >= 32) {  // elements [1024, 2048): the next input block
-#pragma unroll
-      for (int i = 0; i < P; ++i) key[i] = load(next + (int64_t)(lane - 32) * P + i);
-    }
-    dr::wave_sort_desc<P>(key);
-  }
-#pragma unroll
-  for (int i = 0; i < P; ++i) {
-    const int e = lane * P + i;
-    if (e < k_out) {
-      const bool empty = key[i] == 0ull;
-      out_s[u * k_out + e] = empty ? -INFINITY : dr::key_score(key[i]);
-      out_i[u * k_out + e] = empty ? -1 : (int32_t)dr::key_item(key[i]);
-    }
-  }
+    for (int i = 0; i < P; ++i) key[i] = entry(x0 + (int64_t)(lane - lane0) * P + i);
+  });
+  write_best<P>(key, k_out, out_s, out_i, u);
 }
 
 }  // namespace
@@ -939,7 +1147,7 @@ extern "C" int dr_score_topk_fail_counts(const void* workspace, int64_t n_users,
   DR_CHECK_ARG(workspace && n_users > 0 && n_items > 0, "bad arguments");
   const Layout L = make_layout(n_users, n_items, w, k);
   if (L.g.S == 0) return DR_OK;
-  const char* ws = (const char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  const char* ws = (const char*)al256((uintptr_t)workspace);
   int32_t c[3] = {0, 0, 0};  // first tier, second tier, "ran two tiers"
   DR_CHECK_HIP(hipMemcpy(c, ws + L.off_fcnt(), sizeof(c), hipMemcpyDeviceToHost));
   out[0] = c[0];
@@ -958,113 +1166,40 @@ extern "C" size_t dr_score_topk_diag_offset(int64_t n_users, int64_t n_items, in
 }
 #endif
 
+// A guess's fail list: the users a finalize left with fewer than k keys
+// (their table rows and output positions) and their count, on the device.
+struct FailList {
+  int64_t* rows;
+  int64_t* pos;
+  int32_t* cnt;
+};
+
 extern "C" int dr_score_topk(const void* user_table, const int64_t* user_ids, int64_t n_users,
                              const void* item_table, int64_t n_items, int64_t item_base,
                              int dtype, int d, int k, const int64_t* excl_rowptr,
                              const int32_t* excl_items, float* out_scores, int32_t* out_items,
                              void* workspace, size_t workspace_bytes, dr_stream_t stream) {
-  DR_CHECK_ARG(n_users >= 0 && n_items >= 0, "negative size");
-  DR_CHECK_ARG(k >= 1 && k <= 1024, "k must be in [1, 1024]");
-  DR_CHECK_ARG(dtype == DR_BF16 || dtype == DR_F32, "tables must be DR_BF16 or DR_F32");
-  const int w = width_for(dtype, d);
-  DR_CHECK_ARG(w > 0, dtype == DR_BF16 ? "bf16 d must be one of 32, 64, 128, 256, 512"
-                                       : "fp32 d must be one of 32, 64, 128, 256");
-  DR_CHECK_ARG(cap_for(w, k) > 0, "k too large for this d");
-  DR_CHECK_ARG(item_base >= 0 && item_base + n_items < 0x7fffffffLL,
-               "global item ids must fit int32");
-  DR_CHECK_ARG((excl_rowptr == nullptr) == (excl_items == nullptr),
-               "excl_rowptr and excl_items must both be set or both be NULL");
+  const char* fn = __func__;
+  int w = 0;
+  DR_TRY(check_score_call(fn, user_table, n_users, item_table, n_items, item_base, dtype, d, k,
+                          excl_rowptr, excl_items, out_scores, out_items, true, &w));
   if (n_users == 0) return DR_OK;
-  DR_CHECK_ARG(user_table && out_scores && out_items, "null pointer");
-  if (n_items == 0) {
-    dr::set_error("dr_score_topk: empty catalog");
-    return DR_EINVAL;
-  }
-  DR_CHECK_ARG(item_table, "null item_table");
   hipStream_t s = (hipStream_t)stream;
   const Layout L = make_layout(n_users, n_items, w, k);
-  const size_t need = L.total();
-  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  if (!workspace || (size_t)(ws - (char*)workspace) + need > workspace_bytes) {
-    dr::set_error("dr_score_topk: workspace too small (need " + std::to_string(need + 256) +
-                  " bytes)");
-    return DR_EWORKSPACE;
-  }
+  char* ws = workspace_base(fn, workspace, workspace_bytes, L.total());
+  if (!ws) return DR_EWORKSPACE;
   const Plan& p = L.main;
-  TopkArgs a{};
-  a.U = (const char*)user_table;
-  a.user_ids = user_ids;
-  a.n_users = n_users;
-  a.n_users_pad = p.n_users_pad;
-  a.I = (const char*)item_table;
-  a.n_items = n_items;
+  TopkArgs a = args_for(p, user_table, user_ids, n_users, item_table, n_items, k, ws, L.cand);
   a.item_base = item_base;
-  a.k = k;
   a.excl_rowptr = excl_rowptr;
   a.excl_items = excl_items;
-  a.n_ublocks = p.n_ublocks;
-  a.n_head = p.n_head;
-  a.tail_chunks = p.tail_chunks;
-  a.chunk_items = p.chunk_items;
-  a.end_keep = p.end_keep;
-  a.head_keep = p.head_keep;
-  a.slack = p.slack;
-  a.gap = p.gap;
-  a.keep_all = p.keep_all;  // the main scan only (small catalogs: no guess, no rescans)
-  a.init_thr = nullptr;
-  a.n_users_dev = nullptr;
-  a.pos_map = nullptr;
-  a.cand = (uint64_t*)ws;
-  a.cnt = (int32_t*)(ws + L.cand);
   a.diag = (uint64_t*)(ws + L.off_diag());  // written only in DIAG builds
-  const BufMap bm = buf_map(p);
-  const int64_t head_end = p.head_users() < n_users ? p.head_users() : n_users;
+  const FinalizeArgs fin{a.cand, a.cnt, buf_map(p), p.cap, k, excl_rowptr, excl_items,
+                         out_scores, out_items, user_ids};
 
-#define DR_SCAN_OR_FAIL(PLAN, ARGS, SEEDED)                                  \
-  if (!launch_scan(PLAN, ARGS, dtype, w, SEEDED, s)) {                       \
-    dr::set_error("dr_score_topk: internal plan error (no scan instance)"); \
-    return DR_EUNSUPPORTED;                                                  \
-  }
-#define DR_BY_P(PP_EXPR, LAUNCH)                                           \
-  switch (PP_EXPR) {                                                       \
-    case 4: LAUNCH(4); break;                                              \
-    case 8: LAUNCH(8); break;                                              \
-    case 16: LAUNCH(16); break;                                            \
-    case 32: LAUNCH(32); break;                                            \
-    default:                                                               \
-      dr::set_error("dr_score_topk: internal plan error (candidate sort)"); \
-      return DR_EUNSUPPORTED;                                              \
-  }
-  // finalize of users [U0, U1) (one wave each), P sized for their key count
-#define DR_FIN(PP)                                                                             \
-  hipLaunchKernelGGL((topk_finalize_kernel<PP>), dim3((unsigned)dr::ceil_div(U1 - U0, 4)),      \
-                     dim3(256), 0, s, a.cand, a.cnt, FMAP, p.cap, U0, U1, k, excl_rowptr,        \
-                     excl_items, out_scores, out_items, FPOS, FNDEV, FUIDS, FCNT, frows, fpos,   \
-                     FTSRC, fthr)
-  // head users (one buffer each), then the split tail's users (their chunks)
-#define DR_FIN_ALL()                                                        \
-  {                                                                         \
-    const BufMap FMAP = bm;                                                 \
-    int64_t U0 = 0, U1 = head_end;                                          \
-    if (U1 > U0) { DR_BY_P(p_for(head_keys(p, w, k)), DR_FIN) DR_CHECK_LAUNCH(); } \
-    U0 = head_end;                                                          \
-    U1 = n_users;                                                           \
-    if (U1 > U0) { DR_BY_P(p_for(tail_keys(p, w, k)), DR_FIN) DR_CHECK_LAUNCH(); } \
-  }
-
-  if (L.g.S == 0) {
-    DR_SCAN_OR_FAIL(p, a, false)
-    DR_CHECK_LAUNCH();
-    int64_t* frows = nullptr;
-    int64_t* fpos = nullptr;
-    float* fthr = nullptr;
-    const int64_t* FPOS = nullptr;
-    const int32_t* FNDEV = nullptr;
-    const int64_t* FUIDS = user_ids;
-    int32_t* FCNT = nullptr;
-    const float* FTSRC = nullptr;
-    DR_FIN_ALL()
-    return DR_OK;
+  if (L.g.S == 0) {  // plain scan from -inf (keep_all plans included), finalize
+    DR_TRY(run_scan(fn, p, a, dtype, w, false, s));
+    return finalize_head_and_tail(fn, fin, p, w, n_users, s);
   }
 
   // ---- guessed thresholds: sample scan -> thresholds -> seeded scan -> verify
@@ -1072,90 +1207,41 @@ extern "C" int dr_score_topk(const void* user_table, const int64_t* user_ids, in
   float* thr = (float*)(ws + L.off_thr());
   float* thr2 = two_tier ? (float*)(ws + L.off_thr() + L.thr) : nullptr;
   char* samp = ws + L.off_samp();
-  int64_t* frows = (int64_t*)(ws + L.off_frows());
-  int64_t* fpos = (int64_t*)(ws + L.off_fpos());
   float* fthr = two_tier ? (float*)(ws + L.off_fthr()) : nullptr;
-  int64_t* frows2 = (int64_t*)(ws + L.off_frows2());
-  int64_t* fpos2 = (int64_t*)(ws + L.off_fpos2());
   // [0] first-tier failures, [1] second-tier, [2] 1 if this call ran two tiers
   int32_t* fcnt = (int32_t*)(ws + L.off_fcnt());
+  const FailList fail1{(int64_t*)(ws + L.off_frows()), (int64_t*)(ws + L.off_fpos()), fcnt};
+  const FailList fail2{(int64_t*)(ws + L.off_frows2()), (int64_t*)(ws + L.off_fpos2()), fcnt + 1};
   DR_CHECK_HIP(hipMemsetAsync(fcnt, 0, 2 * sizeof(int32_t), s));
   DR_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(fcnt + 2), two_tier ? 1 : 0, 1, s));
-  {
-    const int cpr = w / 8;  // 16-B chunks per row
-    const int64_t n16 = L.g.S * cpr;
-    hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)dr::ceil_div(n16, 256)), dim3(256), 0, s,
-                       (const uint4*)item_table, L.g.stride, L.g.S, cpr, (uint4*)samp);
-    DR_CHECK_LAUNCH();
-  }
-  const Plan& ps = L.sample;
-  TopkArgs as = a;  // sample ids are sample rows: no exclusions, no item base
-  as.I = samp;
-  as.n_items = L.g.S;
-  as.item_base = 0;
-  as.k = L.g.ks;
-  as.excl_rowptr = nullptr;
-  as.excl_items = nullptr;
-  as.n_head = ps.n_head;
-  as.tail_chunks = ps.tail_chunks;
-  as.chunk_items = ps.chunk_items;
-  as.end_keep = ps.end_keep;
-  as.head_keep = ps.head_keep;
-  as.slack = ps.slack;
-  as.gap = ps.gap;
-  as.keep_all = 0;
-  as.gmax = L.dense ? 2 : kSampleGmax;
-  as.tmax = (float*)ws;  // the candidate region
-  as.tmax_tiles = L.g.S / kTileItems;
-  DR_SCAN_OR_FAIL(ps, as, false)
-  DR_CHECK_LAUNCH();
-  if (L.dense) {
-    if (!launch_threshold_dense(as.tmax, as.tmax_tiles, p.n_users_pad, n_users, L.g.ks, L.g.ks1,
-                                thr, thr2, s)) {
-      dr::set_error("dr_score_topk: internal plan error (dense threshold rank)");
-      return DR_EUNSUPPORTED;
-    }
-    DR_CHECK_LAUNCH();
-  } else {
-    const BufMap sm = buf_map(ps);
-    const int64_t sh = ps.head_users();
-#define DR_THR(PP)                                                                             \
-  hipLaunchKernelGGL((topk_threshold_kernel<PP>), dim3((unsigned)dr::ceil_div(T1 - T0, 4)),     \
-                     dim3(256), 0, s, a.cand, a.cnt, sm, ps.cap, T0, T1, n_users, L.g.ks,        \
-                     L.g.ks1, thr, thr2)
-    int64_t T0 = 0, T1 = sh < p.n_users_pad ? sh : p.n_users_pad;
-    if (T1 > T0) { DR_BY_P(p_for(head_keys(ps, w, L.g.ks)), DR_THR) DR_CHECK_LAUNCH(); }
-    T0 = T1;
-    T1 = p.n_users_pad;
-    if (T1 > T0) { DR_BY_P(p_for(tail_keys(ps, w, L.g.ks)), DR_THR) DR_CHECK_LAUNCH(); }
-#undef DR_THR
-  }
+  DR_TRY(copy_sample_rows(fn, item_table, L.g.stride, L.g.S, w, samp, s));
+  TopkArgs as = sample_args(L.sample, user_table, user_ids, n_users, samp, ws, L.cand);
+  as.diag = a.diag;
+  // every buffer position gets a threshold (padding: +inf, no key passes)
+  DR_TRY(sample_scan_thresholds(fn, L.sample, as, dtype, w, L.g.ks1, p.n_users_pad, thr, thr2, s));
 
+  // ---- first tier: the main scan from thr; the finalize lists the users left
+  // with fewer than k keys (and their safe thresholds) in fail1
   a.init_thr = thr;
-  DR_SCAN_OR_FAIL(p, a, true)
-  DR_CHECK_LAUNCH();
-  {
-    const int64_t* FPOS = nullptr;
-    const int32_t* FNDEV = nullptr;
-    const int64_t* FUIDS = user_ids;
-    int32_t* FCNT = fcnt;  // verify: users left with fewer than k keys
-    const float* FTSRC = thr2;
-    DR_FIN_ALL()
-  }
+  DR_TRY(run_scan(fn, p, a, dtype, w, true, s));
+  FinalizeArgs verify = fin;
+  verify.fail_cnt = fail1.cnt;
+  verify.fail_rows = fail1.rows;
+  verify.fail_pos = fail1.pos;
+  verify.fail_thr_src = thr2;
+  verify.fail_thr = fthr;
+  DR_TRY(finalize_head_and_tail(fn, verify, p, w, n_users, s));
 
-  // ---- second tier (two-tier guesses): the first tier's failures rescanned
-  // from their safe thresholds, every failing user block split over the CUs
-  // (plan on the device: the count is there), any number of keys per user
-  // merged by the streaming finalize; its own failures go to the third tier
-  const int64_t* t3_rows = frows;
-  const int64_t* t3_pos = fpos;
-  const int32_t* t3_cnt = fcnt;
+  // ---- second tier (two-tier guesses): fail1's users rescanned from their
+  // safe thresholds, every failing user block split over the CUs (plan on the
+  // device: the count is there), any number of keys per user merged by the
+  // streaming finalize; its own failures go to fail2
   if (two_tier) {
     TopkArgs a2 = a;
     a2.init_thr = fthr;
-    a2.user_ids = frows;
-    a2.pos_map = fpos;
-    a2.n_users_dev = fcnt;
+    a2.user_ids = fail1.rows;
+    a2.pos_map = fail1.pos;
+    a2.n_users_dev = fail1.cnt;
     a2.n_head = 0;
     a2.end_keep = 0;
     a2.keep_all = 0;
@@ -1164,56 +1250,37 @@ extern "C" int dr_score_topk(const void* user_table, const int64_t* user_ids, in
     a2.diag = nullptr;
     Plan p2 = p;
     p2.grid = device_cus();
-    DR_SCAN_OR_FAIL(p2, a2, true)
-    DR_CHECK_LAUNCH();
-    DevSplitArgs dsa;
-    dsa.upwg = p.users_per_wg;
-    dsa.grid = p2.grid;
-    dsa.max_c = kMaxRescanChunks;
-    dsa.buf_blocks = a2.buf_blocks;
-    dsa.n_items = n_items;
-    dsa.stage_items = stage_items_for(w, p.cap);
+    DR_TRY(run_scan(fn, p2, a2, dtype, w, true, s));
+    const DevSplitArgs dsa{p.users_per_wg, p2.grid, kMaxRescanChunks,
+                           a2.buf_blocks,  n_items, stage_items_for(w, p.cap)};
     hipLaunchKernelGGL(topk_finalize_stream_kernel, dim3((unsigned)dr::ceil_div(n_users, 4)),
                        dim3(256), 0, s, a.cand, a.cnt, dsa, p.cap, n_users, k, excl_rowptr,
-                       excl_items, out_scores, out_items, fpos, fcnt, frows, fcnt + 1, frows2,
-                       fpos2);
-    DR_CHECK_LAUNCH();
-    t3_rows = frows2;
-    t3_pos = fpos2;
-    t3_cnt = fcnt + 1;
+                       excl_items, out_scores, out_items, fail1.pos, fail1.cnt, fail1.rows,
+                       fail2.cnt, fail2.rows, fail2.pos);
+    DR_TRY(launch_status(fn));
   }
 
   // ---- third tier: the users every guess failed (usually none), rescanned
   // from -inf; whole-catalog units only, one buffer per listed user
-  TopkArgs af = a;
-  af.init_thr = nullptr;
-  af.user_ids = t3_rows;
-  af.pos_map = t3_pos;
-  af.n_users_dev = t3_cnt;
-  af.n_head = p.n_ublocks;
-  af.tail_chunks = 1;
-  af.chunk_items = n_items;
-  af.end_keep = 0;
-  af.keep_all = 0;
-  af.diag = nullptr;
-  DR_SCAN_OR_FAIL(p, af, false)
-  DR_CHECK_LAUNCH();
-  {
-    const BufMap FMAP{p.n_users_pad, p.n_users_pad, 0, 1};
-    const int64_t U0 = 0, U1 = n_users;
-    const int64_t* FPOS = t3_pos;
-    const int32_t* FNDEV = t3_cnt;
-    const int64_t* FUIDS = t3_rows;
-    int32_t* FCNT = nullptr;
-    const float* FTSRC = nullptr;
-    DR_BY_P(p_for(head_keys(p, w, k)), DR_FIN)
-    DR_CHECK_LAUNCH();
-  }
-#undef DR_FIN_ALL
-#undef DR_FIN
-#undef DR_BY_P
-#undef DR_SCAN_OR_FAIL
-  return DR_OK;
+  const FailList& last = two_tier ? fail2 : fail1;
+  TopkArgs a3 = a;
+  a3.init_thr = nullptr;
+  a3.user_ids = last.rows;
+  a3.pos_map = last.pos;
+  a3.n_users_dev = last.cnt;
+  a3.n_head = p.n_ublocks;
+  a3.tail_chunks = 1;
+  a3.chunk_items = n_items;
+  a3.end_keep = 0;
+  a3.keep_all = 0;
+  a3.diag = nullptr;
+  DR_TRY(run_scan(fn, p, a3, dtype, w, false, s));
+  FinalizeArgs fin3 = fin;
+  fin3.map = BufMap{p.n_users_pad, p.n_users_pad, 0, 1};
+  fin3.user_ids = last.rows;
+  fin3.pos_map = last.pos;
+  fin3.n_users_dev = last.cnt;
+  return finalize_range(fn, fin3, 0, n_users, head_keys(p, w, k), s);
 }
 
 // ------------------------------------------------------------------ caller-seeded scan
@@ -1242,88 +1309,28 @@ extern "C" int dr_score_topk_seeded(const void* user_table, const int64_t* user_
                                     const int32_t* excl_items, float* out_scores,
                                     int32_t* out_items, void* workspace, size_t workspace_bytes,
                                     dr_stream_t stream) {
-  DR_CHECK_ARG(n_users >= 0 && n_items >= 0, "negative size");
-  DR_CHECK_ARG(k >= 1 && k <= 1024, "k must be in [1, 1024]");
-  DR_CHECK_ARG(dtype == DR_BF16 || dtype == DR_F32, "tables must be DR_BF16 or DR_F32");
-  const int w = width_for(dtype, d);
-  DR_CHECK_ARG(w > 0, dtype == DR_BF16 ? "bf16 d must be one of 32, 64, 128, 256, 512"
-                                       : "fp32 d must be one of 32, 64, 128, 256");
-  DR_CHECK_ARG(cap_for(w, k) > 0, "k too large for this d");
-  DR_CHECK_ARG(item_base >= 0 && item_base + n_items < 0x7fffffffLL,
-               "global item ids must fit int32");
-  DR_CHECK_ARG((excl_rowptr == nullptr) == (excl_items == nullptr),
-               "excl_rowptr and excl_items must both be set or both be NULL");
+  const char* fn = __func__;
+  int w = 0;
+  DR_TRY(check_score_call(fn, user_table, n_users, item_table, n_items, item_base, dtype, d, k,
+                          excl_rowptr, excl_items, out_scores, out_items, init_thr != nullptr,
+                          &w));
   if (n_users == 0) return DR_OK;
-  DR_CHECK_ARG(user_table && out_scores && out_items && init_thr, "null pointer");
-  if (n_items == 0) {
-    dr::set_error("dr_score_topk_seeded: empty catalog");
-    return DR_EINVAL;
-  }
-  DR_CHECK_ARG(item_table, "null item_table");
   hipStream_t s = (hipStream_t)stream;
   const Plan p = seeded_plan(n_users, n_items, w, k);
-  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  const size_t need = p.cand_bytes + p.cnt_bytes + diag_bytes();
-  if (!workspace || (size_t)(ws - (char*)workspace) + need > workspace_bytes) {
-    dr::set_error("dr_score_topk_seeded: workspace too small (need " +
-                  std::to_string(need + 256) + " bytes)");
-    return DR_EWORKSPACE;
-  }
-  TopkArgs a{};
-  a.U = (const char*)user_table;
-  a.user_ids = user_ids;
-  a.n_users = n_users;
-  a.n_users_pad = p.n_users_pad;
-  a.I = (const char*)item_table;
-  a.n_items = n_items;
+  char* ws = workspace_base(fn, workspace, workspace_bytes,
+                            p.cand_bytes + p.cnt_bytes + diag_bytes());
+  if (!ws) return DR_EWORKSPACE;
+  TopkArgs a = args_for(p, user_table, user_ids, n_users, item_table, n_items, k, ws,
+                        p.cand_bytes);
   a.item_base = item_base;
-  a.k = k;
   a.excl_rowptr = excl_rowptr;
   a.excl_items = excl_items;
-  a.n_ublocks = p.n_ublocks;
-  a.n_head = p.n_head;
-  a.tail_chunks = p.tail_chunks;
-  a.chunk_items = p.chunk_items;
-  a.end_keep = p.end_keep;
-  a.head_keep = p.head_keep;
-  a.slack = p.slack;
-  a.gap = p.gap;
   a.init_thr = init_thr;
-  a.cand = (uint64_t*)ws;
-  a.cnt = (int32_t*)(ws + p.cand_bytes);
   a.diag = (uint64_t*)(ws + p.cand_bytes + p.cnt_bytes);
-  if (!launch_scan(p, a, dtype, w, true, s)) {
-    dr::set_error("dr_score_topk_seeded: internal plan error (no scan instance)");
-    return DR_EUNSUPPORTED;
-  }
-  DR_CHECK_LAUNCH();
-  const BufMap bm = buf_map(p);
-  const int64_t head_end = p.head_users() < n_users ? p.head_users() : n_users;
-  int64_t U0 = 0, U1 = head_end;
-  for (int part = 0; part < 2; ++part) {
-    if (U1 > U0) {
-      const int P = p_for(part == 0 ? head_keys(p, w, k) : tail_keys(p, w, k));
-      const dim3 grid((unsigned)dr::ceil_div(U1 - U0, 4));
-#define DR_FIN_SEEDED(PP)                                                                       \
-  hipLaunchKernelGGL((topk_finalize_kernel<PP>), grid, dim3(256), 0, s, a.cand, a.cnt, bm, p.cap, \
-                     U0, U1, k, excl_rowptr, excl_items, out_scores, out_items, nullptr, nullptr,  \
-                     user_ids, nullptr, nullptr, nullptr, nullptr, nullptr)
-      switch (P) {
-        case 4: DR_FIN_SEEDED(4); break;
-        case 8: DR_FIN_SEEDED(8); break;
-        case 16: DR_FIN_SEEDED(16); break;
-        case 32: DR_FIN_SEEDED(32); break;
-        default:
-          dr::set_error("dr_score_topk_seeded: internal plan error (candidate sort)");
-          return DR_EUNSUPPORTED;
-      }
-#undef DR_FIN_SEEDED
-      DR_CHECK_LAUNCH();
-    }
-    U0 = head_end;
-    U1 = n_users;
-  }
-  return DR_OK;
+  DR_TRY(run_scan(fn, p, a, dtype, w, true, s));
+  const FinalizeArgs fin{a.cand, a.cnt, buf_map(p), p.cap, k, excl_rowptr, excl_items,
+                         out_scores, out_items, user_ids};
+  return finalize_head_and_tail(fn, fin, p, w, n_users, s);
 }
 
 // ------------------------------------------------------------------ sample thresholds
@@ -1331,37 +1338,11 @@ extern "C" int dr_score_topk_seeded(const void* user_table, const int64_t* user_
 // (divrec.distributed.global_thresholds): tile-transposed copy of the whole
 // tiles of the sample, the GMAX sample scan (k = ks), thresholds at ranks ks1
 // and ks. Workspace: [cand | cnt | transposed sample].
-struct SampleThrLayout {
-  Plan p;
-  int64_t S = 0;
-  bool dense = false;
-  size_t cand = 0, cnt = 0, samp = 0;
-  size_t total() const { return cand + cnt + samp; }
-};
-
-SampleThrLayout sample_thr_layout(int64_t n_users, int64_t n_sample, int w, int ks) {
-  SampleThrLayout L;
-  L.S = n_sample / kTileItems * kTileItems;
-  if (L.S == 0) return L;
-  L.p = make_plan(n_users, L.S, w, ks, false);
-  L.p.slack = kSampleSlack;
-  L.p.gap = kSampleGap;
-  L.dense = sample_dense(ks, L.p.n_users_pad, L.S);
-  L.cand = al256(L.dense ? dense_bytes(L.p.n_users_pad, L.S) : L.p.cand_bytes);
-  L.cnt = al256(L.p.cnt_bytes);
-  L.samp = al256((size_t)L.S * w * 2);
-  return L;
+SampleScan sample_thr_scan(int64_t n_users, int64_t n_sample, int w, int ks) {
+  return sample_scan_for(n_users, n_sample / kTileItems * kTileItems, w, ks);
 }
-
-// out row p = 32 r + q <- sample row q T + r (T = S / 32), 16 B per thread
-__global__ __launch_bounds__(256) void transpose_tiles_kernel(const uint4* __restrict__ in,
-                                                              int64_t S, int cpr,
-                                                              uint4* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= S * cpr) return;
-  const int64_t p = t / cpr, c = t % cpr;
-  const int64_t T = S / kTileItems;
-  out[t] = in[((p % kTileItems) * T + p / kTileItems) * cpr + c];
+size_t sample_thr_bytes(const SampleScan& ss, int w) {
+  return ss.cand_bytes + ss.plan.cnt_bytes + al256((size_t)ss.S * w * 2);
 }
 
 __global__ __launch_bounds__(256) void fill_f32_kernel(float* __restrict__ a, float* __restrict__ b,
@@ -1378,13 +1359,14 @@ extern "C" size_t dr_sample_thresholds_workspace(int64_t n_users, int64_t n_samp
   if (n_users <= 0 || n_sample < 0 || ks <= 0 || ks > 256) return 0;
   const int w = width_for(dtype, d);
   if (w < 0 || cap_for(w, ks) < 0) return 0;
-  return sample_thr_layout(n_users, n_sample, w, ks).total() + 256;
+  return sample_thr_bytes(sample_thr_scan(n_users, n_sample, w, ks), w) + 256;
 }
 
 extern "C" int dr_sample_thresholds(const void* user_table, const int64_t* user_ids,
                                     int64_t n_users, const void* sample_rows, int64_t n_sample,
                                     int dtype, int d, int ks1, int ks, float* thr1, float* thr2,
                                     void* workspace, size_t workspace_bytes, dr_stream_t stream) {
+  const char* fn = __func__;
   DR_CHECK_ARG(n_users >= 0 && n_sample >= 0, "negative size");
   DR_CHECK_ARG(ks >= 1 && ks <= 256 && ks1 >= 1 && ks1 <= ks, "need 1 <= ks1 <= ks <= 256");
   DR_CHECK_ARG(dtype == DR_BF16 || dtype == DR_F32, "tables must be DR_BF16 or DR_F32");
@@ -1393,87 +1375,20 @@ extern "C" int dr_sample_thresholds(const void* user_table, const int64_t* user_
   if (n_users == 0) return DR_OK;
   DR_CHECK_ARG(user_table && thr1 && thr2, "null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const SampleThrLayout L = sample_thr_layout(n_users, n_sample, w, ks);
-  if (L.S == 0) {  // no whole tile of sample rows: no guess
+  const SampleScan ss = sample_thr_scan(n_users, n_sample, w, ks);
+  if (ss.S == 0) {  // no whole tile of sample rows: no guess
     hipLaunchKernelGGL(fill_f32_kernel, dim3((unsigned)dr::ceil_div(n_users, 256)), dim3(256), 0, s,
                        thr1, thr2, n_users, -INFINITY);
-    DR_CHECK_LAUNCH();
-    return DR_OK;
+    return launch_status(fn);
   }
   DR_CHECK_ARG(sample_rows, "null sample_rows");
-  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  if (!workspace || (size_t)(ws - (char*)workspace) + L.total() > workspace_bytes) {
-    dr::set_error("dr_sample_thresholds: workspace too small (need " +
-                  std::to_string(L.total() + 256) + " bytes)");
-    return DR_EWORKSPACE;
-  }
-  char* samp = ws + L.cand + L.cnt;
-  {
-    const int cpr = w / 8;
-    hipLaunchKernelGGL(transpose_tiles_kernel, dim3((unsigned)dr::ceil_div(L.S * cpr, 256)),
-                       dim3(256), 0, s, (const uint4*)sample_rows, L.S, cpr, (uint4*)samp);
-    DR_CHECK_LAUNCH();
-  }
-  const Plan& p = L.p;
-  TopkArgs a{};
-  a.U = (const char*)user_table;
-  a.user_ids = user_ids;
-  a.n_users = n_users;
-  a.n_users_pad = p.n_users_pad;
-  a.I = samp;
-  a.n_items = L.S;
-  a.k = ks;
-  a.n_ublocks = p.n_ublocks;
-  a.n_head = p.n_head;
-  a.tail_chunks = p.tail_chunks;
-  a.chunk_items = p.chunk_items;
-  a.end_keep = p.end_keep;
-  a.head_keep = p.head_keep;
-  a.slack = p.slack;
-  a.gap = p.gap;
-  a.gmax = L.dense ? 2 : 1;
-  a.tmax = (float*)ws;
-  a.tmax_tiles = L.S / kTileItems;
-  a.cand = (uint64_t*)ws;
-  a.cnt = (int32_t*)(ws + L.cand);
-  if (!launch_scan(p, a, dtype, w, false, s)) {
-    dr::set_error("dr_sample_thresholds: internal plan error (no scan instance)");
-    return DR_EUNSUPPORTED;
-  }
-  DR_CHECK_LAUNCH();
-  if (L.dense) {
-    if (!launch_threshold_dense(a.tmax, a.tmax_tiles, n_users, n_users, ks, ks1, thr1, thr2, s)) {
-      dr::set_error("dr_sample_thresholds: internal plan error (dense threshold rank)");
-      return DR_EUNSUPPORTED;
-    }
-    DR_CHECK_LAUNCH();
-    return DR_OK;
-  }
-  const BufMap sm = buf_map(p);
-  const int64_t sh = p.head_users() < n_users ? p.head_users() : n_users;
-  int64_t T0 = 0, T1 = sh;
-  for (int part = 0; part < 2; ++part) {
-    if (T1 > T0) {
-      const int P = p_for(part == 0 ? head_keys(p, w, ks) : tail_keys(p, w, ks));
-#define DR_STHR(PP)                                                                              \
-  hipLaunchKernelGGL((topk_threshold_kernel<PP>), dim3((unsigned)dr::ceil_div(T1 - T0, 4)),      \
-                     dim3(256), 0, s, a.cand, a.cnt, sm, p.cap, T0, T1, n_users, ks, ks1, thr1, thr2)
-      switch (P) {
-        case 4: DR_STHR(4); break;
-        case 8: DR_STHR(8); break;
-        case 16: DR_STHR(16); break;
-        case 32: DR_STHR(32); break;
-        default:
-          dr::set_error("dr_sample_thresholds: internal plan error (candidate sort)");
-          return DR_EUNSUPPORTED;
-      }
-#undef DR_STHR
-      DR_CHECK_LAUNCH();
-    }
-    T0 = sh;
-    T1 = n_users;
-  }
-  return DR_OK;
+  char* ws = workspace_base(fn, workspace, workspace_bytes, sample_thr_bytes(ss, w));
+  if (!ws) return DR_EWORKSPACE;
+  char* samp = ws + ss.cand_bytes + ss.plan.cnt_bytes;
+  DR_TRY(copy_sample_rows(fn, sample_rows, 1, ss.S, w, samp, s));
+  const TopkArgs a = sample_args(ss, user_table, user_ids, n_users, samp, ws, ss.cand_bytes);
+  // the caller's arrays hold n_users thresholds: no padding positions
+  return sample_scan_thresholds(fn, ss, a, dtype, w, ks1, n_users, thr1, thr2, s);
 }
 
 extern "C" int dr_topk_merge(const float* in_scores, const int32_t* in_items, int parts,
@@ -1494,17 +1409,17 @@ extern "C" int dr_topk_merge(const float* in_scores, const int32_t* in_items, in
     DR_CHECK_LAUNCH();
     return DR_OK;
   }
-#define DR_MERGE(PP)                                                                        \
-  hipLaunchKernelGGL((topk_merge_kernel<PP>), dim3(grid), dim3(256), 0, s, in_scores,       \
-                     in_items, parts, n_users, k_in, k_out, out_scores, out_items)
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, in_scores, in_items, parts, n_users,
+                       k_in, k_out, out_scores, out_items);
+  };
   switch (p_for((int)total)) {
-    case 2: DR_MERGE(2); break;
-    case 4: DR_MERGE(4); break;
-    case 8: DR_MERGE(8); break;
-    case 16: DR_MERGE(16); break;
-    default: DR_MERGE(32); break;
+    case 2: go(topk_merge_kernel<2>); break;
+    case 4: go(topk_merge_kernel<4>); break;
+    case 8: go(topk_merge_kernel<8>); break;
+    case 16: go(topk_merge_kernel<16>); break;
+    default: go(topk_merge_kernel<32>); break;
   }
-#undef DR_MERGE
   DR_CHECK_LAUNCH();
   return DR_OK;
 }

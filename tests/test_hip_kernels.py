@@ -1233,6 +1233,38 @@ def test_sample_thresholds_group_max(d, n_sample, ks1, ks, ids, dense):
     assert torch.equal(out.cpu(), ref)
 
 
+@pytest.mark.parametrize("n_sample,knobs", [(64, {"scan_slots": 2}),
+                                            (131072, {"scan_slots": 2, "scan_split": 2})])
+def test_sample_thresholds_position_ranges_match_dense(n_sample, knobs):
+    """dr_sample_thresholds over three user blocks on two planned slots, the
+    compaction path (sample_dense = 0: topk_threshold_kernel per position
+    range) against the dense tile maxima, bit for bit. A 64-row sample is two
+    tiles and no planner rule splits it: one range over every position. The
+    planner splits a sample only from 2 x 65536 rows with scan_split forced,
+    so 131072 rows give two head blocks (one buffer per user) and a tail block
+    in two chunks (two buffers): both ranges, shown by dr_score_topk_plan,
+    which plans that many rows at that rank exactly as the sample scan does.
+    31 rows hold no whole tile: -inf for every user."""
+    rng = np.random.default_rng(n_sample)
+    d, ks1, ks, nu = 32, 2, 5, 2 * 2048 + 100
+    Ub, Sb = _bf16(_int_table(rng, nu, d)), _bf16(_int_table(rng, n_sample, d))
+    out = {}
+    with _backend.plan_knobs(**knobs):
+        plan = ops.score_topk_plan(nu, n_sample, torch.bfloat16, d, ks)
+        for dense in (1, 0):
+            with _backend.plan_knobs(sample_dense=dense):
+                out[dense] = ops.sample_thresholds(Ub, Sb, ks1, ks).cpu()
+        none = ops.sample_thresholds(Ub, Sb[:31], ks1, ks).cpu()
+    assert plan["user_blocks"] == 3
+    if n_sample > 64:
+        assert (plan["head_blocks"], plan["tail_chunks"], plan["sample_stride"]) == (2, 2, 0)
+    else:
+        assert torch.isinf(out[1][1]).all()  # two tiles: no 5th best
+    assert torch.isfinite(out[1][0]).all() and (out[1][1] <= out[1][0]).all()
+    assert torch.equal(out[0], out[1])
+    assert torch.equal(none, torch.full((2, nu), -float("inf")))
+
+
 @pytest.mark.parametrize("d,k,dtype", [(64, 100, torch.bfloat16), (128, 100, torch.bfloat16),
                                        (32, 20, torch.bfloat16), (64, 100, torch.float32),
                                        (128, 1000, torch.bfloat16)])

@@ -197,6 +197,47 @@ def test_second_tier_hot_rows_exact():
     _check(Ub, Ib, it, s, np.arange(0, nu, 3), k)
 
 
+def test_third_tier_after_two_tiers_position_map_and_exclusions():
+    """The one path where the rescans' position map, both fail lists and the
+    exclusion row index are live at once. 96 users, a permuted subset of a
+    300-row table, over the smallest seedable catalog (2^18 rows, bf16,
+    d = 32, k = 10: sample stride 32, two tiers). 12 hot rows at sample
+    positions (>= the safe sample rank and >= k) are the best items of every
+    (non-negative) user, so every threshold sits just below the hot score and
+    the scans keep the 12 hot keys only. A user that does not exclude them has
+    its k keys: first tier. A user whose exclusion list holds all 12 is left
+    with none after the first tier AND after the second (its safe threshold
+    is the hot score too), and is rescanned from -inf through the second
+    tier's fail list: both failure counts equal the number of such users, and
+    every list is exact."""
+    rng = np.random.default_rng(20261019)
+    d, ni, k, n_tab, nu = 32, 1 << 18, 10, 300, 96
+    plan = ops.score_topk_plan(nu, ni, torch.bfloat16, d, k)
+    stride, ks, ks1 = plan["sample_stride"], plan["sample_rank"], plan["first_tier_rank"]
+    n_hot = 12
+    assert stride == 32 and ks1 < ks <= n_hot and k <= n_hot
+    U = rng.integers(0, 4, size=(n_tab, d)).astype(np.float32)
+    U[:, 0] = 1.0  # no all-zero user: the hot score is strictly the best
+    I = rng.integers(-3, 4, size=(ni, d)).astype(np.float32)
+    hot = np.arange(n_hot) * stride
+    I[hot] = 3.0
+    users = rng.permutation(n_tab)[:nu].astype(np.int64)
+    frozen = [rng.choice(ni, size=int(rng.integers(0, 20)), replace=False) for _ in users]
+    frozen = [np.setdiff1d(f, hot) for f in frozen]
+    failing = np.unique(np.concatenate([np.arange(0, nu, 3), [1, nu - 1]]))
+    for n in failing:  # all hot rows, and some of the user's best other items
+        best = np.argsort(-(I @ U[users[n]]), kind="stable")[n_hot:n_hot + 5]
+        frozen[n] = np.union1d(frozen[n], np.concatenate([hot, best]))
+    rowptr, cols = oracle.exclusion_csr(frozen)
+    Ub, Ib = torch.from_numpy(U).to(DEV).to(torch.bfloat16), torch.from_numpy(I).to(DEV).to(torch.bfloat16)
+    st = {}
+    s, it = ops.score_topk(Ub, Ib, k, user_ids=torch.from_numpy(users).to(DEV),
+                           exclude=(torch.from_numpy(rowptr).to(DEV),
+                                    torch.from_numpy(cols).to(DEV)), stats=st)
+    assert st["guess_failures"] == [len(failing), len(failing)], st
+    _check(Ub, Ib, it, s, np.arange(nu), k, frozen, users)
+
+
 # --------------------------------------------------------------------------- full size
 def _sample_rows(rng, plan, n_users, n_head, n_tail, n_last):
     """Positions from head blocks, from split-tail blocks and from the last
