@@ -24,6 +24,8 @@
 //     of ONE user: the hot epilogue is a 16-way max and one compare with that
 //     user's running threshold. Scores never leave registers. The two waves of
 //     a SIMD cover each other's epilogues.
+//     The bf16 d = 128 direct-store scans (mfma16_scan) run the same wave tile
+//     on 16x16x32 MFMAs: user tiles of 16, a lane holds 8 scores of one user.
 //   * Survivors are stored straight into per-user candidate buffers in HBM
 //     (slot from a per-user LDS counter), or for W <= 64 staged in LDS and
 //     resolved per stage. Once a buffer holds more than k + kSlack + kFlushGap
@@ -141,6 +143,19 @@ constexpr bool half_issue(int w, int cap, bool f32, bool gmax) {
   return w == 128 && !f32 && !gmax && !long_staged(w, cap);
 }
 
+// Which scans run on v_mfma_f32_16x16x32_bf16 instead of 32x32x16: the same
+// set, which holds every scan that stores keys of a k <= ~670 list at d = 128
+// (main scan and both rescan tiers), so all keys of one list come from one
+// MFMA shape (the two may round their fp32 sums differently). Cycles per flop
+// are equal; the chip holds a higher clock on the 16x16x32 stream. One-process
+// A/B against the 32x32x16 form of the same scans (profiles/mfma16/): -10.5 %
+// at 1M x 10M, k = 100, -6.5 % at 1M x 1.25M (DESIGN.md §3.1 "The other MFMA
+// shape"). The sample scans, the staged long-list instance, other widths and
+// fp32 keep 32x32 shapes (not measured).
+constexpr bool mfma16_scan(int w, int cap, bool f32, bool gmax) {
+  return half_issue(w, cap, f32, gmax);
+}
+
 // D = W, the row's width in bf16 units (row bytes / 2); HALF: half_issue()
 template <int D, int CAP, bool HALF = false>
 struct TileGeom {
@@ -202,6 +217,13 @@ __device__ __forceinline__ void st64(uint64_t* p, uint64_t v) {
 __device__ __forceinline__ u32x4 ds_read_b128_asm(uint32_t lds_addr) {
   u32x4 v;
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr));
+  return v;
+}
+template <int OFF>
+__device__ __forceinline__ u32x4 ds_read_b128_asm_off(uint32_t lds_addr) {
+  static_assert(OFF >= 0 && OFF < 65536 && OFF % 16 == 0, "ds offset field");
+  u32x4 v;
+  asm volatile("ds_read_b128 %0, %1 offset:%c2" : "=v"(v) : "v"(lds_addr), "i"(OFF));
   return v;
 }
 // LDS waits that name the fragment they retire ("+v"): no consumer of it can
@@ -366,7 +388,7 @@ __device__ __forceinline__ float hot_max16(const f32x16& a) {
 __device__ __forceinline__ bool hot(float m, float thr) { return !(m <= thr); }
 
 // Item row (within its tile) of score register r of a lane of half-wave h.
-__device__ __forceinline__ int score_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+__host__ __device__ constexpr int score_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 // The partial-tile rule: bit r is set iff score register r is a row of the
 // slice, `left` rows of which remain from the tile's first (all 16 but in the
 // slice's last tile, whose rows past the end repeat the last row).
@@ -376,6 +398,29 @@ __device__ __forceinline__ uint32_t valid_rows(int64_t left, int h) {
     vmask = 0u;
 #pragma unroll
     for (int r = 0; r < 16; ++r) vmask |= (score_row(r, h) < (int)left ? 1u : 0u) << r;
+  }
+  return vmask;
+}
+
+// The 16x16x32 scans (mfma16_scan): a lane of lane group q = lane / 16 holds 8
+// scores of one user, registers j = 0..3 of the tile's two 16-row halves:
+// rows 16 * half + 4 q + j. Score register b = 4 * half + j.
+__device__ __forceinline__ float hot_max8(const dr::f32x4& a0, const dr::f32x4& a1) {
+  float m = __builtin_elementwise_maximum(a0[0], a0[1]);
+#pragma unroll
+  for (int j = 2; j < 4; ++j) m = __builtin_elementwise_maximum(m, a0[j]);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) m = __builtin_elementwise_maximum(m, a1[j]);
+  return m;
+}
+__host__ __device__ constexpr int score_row16(int b, int q) { return 16 * (b >> 2) + (b & 3) + 4 * q; }
+// valid_rows for that layout: bit b is set iff score register b is a row of the slice
+__device__ __forceinline__ uint32_t valid_rows16(int64_t left, int q) {
+  uint32_t vmask = 0xffu;
+  if (left < kTileItems) {
+    vmask = 0u;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) vmask |= (score_row16(b, q) < (int)left ? 1u : 0u) << b;
   }
   return vmask;
 }
@@ -630,6 +675,13 @@ __device__ __forceinline__ f32x16 kstep1(const u32x4& av, const u32x4& bv, f32x1
   }
 }
 
+// One 32-wide k-step of the 16x16x32 scans against one user tile of 16: lane
+// (row r, group q) holds A[row r][k = 32s + 8q .. +7] and the same k of user r.
+__device__ __forceinline__ dr::f32x4 kstep16(const u32x4& av, const u32x4& bv, dr::f32x4 acc) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av),
+                                                 __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
+}
+
 struct TopkArgs {
   const char* U;  // user table rows: W * 2 bytes each
   const int64_t* user_ids;
@@ -739,6 +791,17 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
   constexpr int NGRP = NU_T / NG;    // groups scored against each item tile
   static_assert(NGRP * NG == NU_T && NGRP <= 2, "user tile groups");
   constexpr int KS = G::KSTEPS;
+  // The MFMA shape. 32x32x16 (and the fp32 form): user tiles of 32, a lane's
+  // 16-B chunk of a k-step is its half-wave's (2 per k-step of 16). 16x16x32
+  // (M16): user tiles of 16, k-steps of 32, the chunk is the lane group's
+  // (lane / 16; 4 per k-step). The wave's users, its B-fragment registers and
+  // its LDS counters are the same either way.
+  constexpr bool M16 = mfma16_scan(W, CAP, F32, GMAX);
+  constexpr int TU = M16 ? 16 : 32;          // users per MFMA user tile
+  constexpr int NT = NU_T * 32 / TU;         // user tiles (thresholds) per lane
+  constexpr int KQ = M16 ? 4 : 2;            // 16-B chunks per k-step
+  constexpr int KF = KS * 2 / KQ;            // k-steps (B fragments) per user tile
+  static_assert(!M16 || (NGRP == 1 && D == 128), "the 16x16x32 form is the d = 128 direct-store scan");
   constexpr int SR = G::SR;
   constexpr int UPW = NU_T * 32;      // users per wave
   constexpr int kWaves = G::WAVES;
@@ -797,6 +860,15 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
   const uint32_t a_row = (uint32_t)(col * (2 * D));
   const uint32_t a_sw = (uint32_t)(h ^ G::swz(col));
   auto a_off = [&](int s) -> uint32_t { return a_row + ((((uint32_t)(2 * s)) ^ a_sw) << 4); };
+  // M16: the lane's user (and item row within a half tile) and its 16-B chunk
+  // within a k-step. Row 16 * half + ucol swizzles by ucol, so the offset of
+  // k-step s is a_row16 + half * 16 rows + ((4s + kq) ^ ucol) * 16, and 4s + kq
+  // = 4s ^ kq: the same two VALU per read, the half an instruction offset.
+  const int ucol = M16 ? (lane & 15) : col;
+  const int kq = M16 ? (lane >> 4) : h;
+  const uint32_t a_row16 = (uint32_t)(ucol * (2 * D));
+  const uint32_t a_sw16 = (uint32_t)(kq ^ G::swz(ucol));
+  auto a_off16 = [&](int s) -> uint32_t { return a_row16 + ((((uint32_t)(4 * s)) ^ a_sw16) << 4); };
 
 #ifdef DR_TOPK_DIAG
   uint64_t dg[kDgSlots] = {};
@@ -856,17 +928,18 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
                        (size_t)((i_beg >> 5) + t)) * 32;
     };
 
-    // Resident B fragments: lane holds user (ut*32+col), k = 16s + 8h .. +7.
-    u32x4 bfr[NU_T][KS];  // bf16x8 (bf16 tables) or f32x4 (fp32 tables) per k-step
-    float thr[NU_T];
+    // Resident B fragments: lane holds user (ut*32+col), k = 16s + 8h .. +7
+    // (M16: user ut*16 + ucol, k = 32s + 8 kq .. +7).
+    u32x4 bfr[NT][KF];  // bf16x8 (bf16 tables) or f32x4 (fp32 tables) per k-step
+    float thr[NT];
 #pragma unroll
-    for (int ut = 0; ut < NU_T; ++ut) {
-      const int64_t pos = upos0 + ut * 32 + col;
+    for (int ut = 0; ut < NT; ++ut) {
+      const int64_t pos = upos0 + ut * TU + ucol;
       int64_t row = 0;
       if (pos < n_users) row = a.user_ids ? a.user_ids[pos] : pos;
-      const uint4* src = reinterpret_cast<const uint4*>(a.U + row * (2 * D) + 16 * h);
+      const uint4* src = reinterpret_cast<const uint4*>(a.U + row * (2 * D) + 16 * kq);
 #pragma unroll
-      for (int s = 0; s < KS; ++s) bfr[ut][s] = __builtin_bit_cast(u32x4, src[2 * s]);
+      for (int s = 0; s < KF; ++s) bfr[ut][s] = __builtin_bit_cast(u32x4, src[KQ * s]);
       thr[ut] = SEEDED ? (pos < n_users ? a.init_thr[pos] : INFINITY) : -INFINITY;
     }
     // Retire those loads where the compiler can see it (else it waits for them
@@ -910,7 +983,7 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
     // -------------------------------------------------------------- cold paths
     auto compact = [&](int ut, int c, int n_in, int slack) {
       DG_T0(t_f);
-      const int slot = ut * 32 + c;
+      const int slot = ut * TU + c;
       const int64_t upos = upos0 + slot;
       const int32_t* ex = nullptr;
       int exn = 0;
@@ -931,8 +1004,8 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
       if (lane == 0) ucnt[slot] = (uint32_t)r.kept;
       wave_lds_sync();
 #pragma unroll
-      for (int u2 = 0; u2 < NU_T; ++u2)
-        if (u2 == ut && col == c) thr[u2] = fmaxf(thr[u2], r.thr);  // both bounds are valid
+      for (int u2 = 0; u2 < NT; ++u2)  // every lane of the user (2; M16: 4)
+        if (u2 == ut && ucol == c) thr[u2] = fmaxf(thr[u2], r.thr);  // both bounds are valid
       DG_ADD(kDgFlush, t_f);
       DG_CNT(kDgNFlush);
     };
@@ -940,9 +1013,9 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
     // buffers above lim are compacted down to k + slack keys
     auto check_compact = [&](int lim, int slack) {
 #pragma unroll
-      for (int ut = 0; ut < NU_T; ++ut) {
-        const uint32_t c_cnt = ucnt[ut * 32 + col];
-        uint64_t need = __ballot(c_cnt > (uint32_t)lim) & 0xffffffffull;
+      for (int ut = 0; ut < NT; ++ut) {
+        const uint32_t c_cnt = ucnt[ut * TU + ucol];
+        uint64_t need = __ballot(c_cnt > (uint32_t)lim) & ((1ull << TU) - 1ull);
         while (need) {
           const int c = __builtin_ctzll(need);
           need &= need - 1;
@@ -987,20 +1060,37 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
     // vmc is bumped under wave-uniform branches only and stays in an SGPR.
     // gbase_h (the item id of the lane's score register 0) belongs to the item
     // tile and is passed in, as the partial-tile rule is applied there.
-    auto enqueue_ut = [&](const f32x16& ac, auto UI, uint32_t gbase_h) {
+    // M16: the same with 8 score registers b = 4 * half + j of the user tile's
+    // two accumulators, rows score_row16(b, kq), and a tree over 8 ballots. The
+    // lanes of one block may be up to four of one user (rows 4 apart); the LDS
+    // atomic gives each its own slot.
+    auto enqueue_ut = [&](const auto& ac, auto UI, uint32_t gbase_h) {
       constexpr int u = decltype(UI)::value;
-      const int slot = u * 32 + col;
+      constexpr int NR = M16 ? 8 : 16;
+      // M16 has 8 user tiles: their buffer addresses hoisted out of the tile
+      // loop would take 16 registers it does not have (a B fragment spilled),
+      // so the lane's column is made opaque here, as in issue_stage
+      uint32_t uc = (uint32_t)ucol;
+      if constexpr (M16) asm volatile("" : "+v"(uc));
+      const int slot = u * TU + (int)uc;
       uint64_t* ubuf = cbase + (size_t)slot * CAP;  // this lane's user buffer
-      uint64_t m[16];
+      float sc[NR];  // the score registers, by name
 #pragma unroll
-      for (int r = 0; r < 16; ++r) m[r] = __ballot(ac[r] > thr[u]);  // strict: never a NaN score
+      for (int r = 0; r < NR; ++r) {
+        if constexpr (M16) sc[r] = ac[r >> 2][u][r & 3];
+        else sc[r] = ac[r];
+      }
+      uint64_t m[NR];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) m[r] = __ballot(sc[r] > thr[u]);  // strict: never a NaN score
       auto block = [&](auto RI) {
         constexpr int r = decltype(RI)::value;
+        constexpr int row = M16 ? score_row16(r, 0) : score_row(r, 0);
         if (m[r] == 0ull) return;
         if (__builtin_amdgcn_inverse_ballot_w64(m[r])) {
           const uint32_t pos = atomicAdd(&ucnt[slot], 1u);
           if (pos < (uint32_t)CAP)  // always true (flush_at + MARGIN <= CAP): a guard only
-            st64(ubuf + pos, dr::make_key(ac[r], gbase_h + (uint32_t)score_row(r, 0)));
+            st64(ubuf + pos, dr::make_key(sc[r], gbase_h + (uint32_t)row));
         }
         vmc += 1;  // the store above issued once (some lane had a key)
       };
@@ -1020,7 +1110,7 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
         }
       };
       blocks(blocks, IC<0>{}, IC<8>{});
-      blocks(blocks, IC<8>{}, IC<8>{});
+      if constexpr (!M16) blocks(blocks, IC<8>{}, IC<8>{});
     };
     auto enqueue = [&](int t, f32x16 (&acc)[NG], const uint64_t (&hb)[NG], auto GI) {
       constexpr int g0 = decltype(GI)::value * NG;
@@ -1043,6 +1133,76 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
       static_for<0, NG>([&](auto J) {
         constexpr int j = decltype(J)::value;
         if (hb[j] != 0ull) enqueue_ut(acc[j], IC<g0 + j>{}, gbase_h);
+      });
+      DG_ADD(kDgEnqueue, t_e);
+      DG_CNT(kDgNEnqueue);
+    };
+
+    // ------------------------------------------------- the 16x16x32 tile (M16)
+    // The same output tile per wave (128 users x 32 items), the same 8
+    // ds_read_b128, 64 accumulator registers and 1024 MFMA cycles: fragment
+    // f = 4 * half + s (rows 16 * half .., k-step s of 32) is read two fragments
+    // before its 8 MFMAs, one per user tile of 16, into acc[half][ut]. (k-step
+    // major, f = 2 s + half, spilled three B fragments in the loop.)
+    auto mma_tile16 = [&](int t, auto& acc) {  // acc: f32x4[2][NT]
+      const uint32_t tb = tile_lds(t);
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int ut = 0; ut < NT; ++ut) acc[hf][ut] = dr::f32x4{};
+      u32x4 af[8];
+      auto read = [&](auto FI) {
+        constexpr int f = decltype(FI)::value;
+        af[f] = ds_read_b128_asm_off<(f / 4) * 16 * 2 * D>(tb + a_off16(f % 4));
+      };
+      read(IC<0>{});
+      read(IC<1>{});
+      static_for<0, 8>([&](auto FI) {
+        constexpr int f = decltype(FI)::value;
+        if constexpr (f + 1 < 8) lds_wait1(af[f]);
+        else lds_wait0(af[f]);
+        if constexpr (f + 2 < 8) read(IC<f + 2>{});
+        // The read stays in front of its group: there every result of the
+        // previous group is still live, so the registers it may be given were
+        // last written by an MFMA at least a whole group earlier (hipcc puts
+        // no wait states between an MFMA's write and an asm's: asm_audit.py).
+        __builtin_amdgcn_sched_barrier(0);
+        if (f == 0 && t == stage_t0) DG_SINCE(kDgBFirst, kDgBMark);
+#pragma unroll
+        for (int ut = 0; ut < NT; ++ut) acc[f / 4][ut] = kstep16(af[f], bfr[ut][f % 4], acc[f / 4][ut]);
+        // a fragment's MFMAs stay together: moved across the waits, they keep
+        // all 8 fragments live, and a B fragment spills (a vmcnt(0) per tile)
+        __builtin_amdgcn_sched_barrier(0);
+      });
+    };
+    // Hot test: a user's 32 scores of the tile sit in 8 registers of each of
+    // its 4 lanes; each lane tests its own 8 against the user's threshold and
+    // the ballot spans the lanes.
+    auto any_hits16 = [&](const auto& acc, uint64_t (&hb)[NT]) -> uint64_t {
+      uint64_t any = 0ull;
+#pragma unroll
+      for (int ut = 0; ut < NT; ++ut) {
+        hb[ut] = __ballot(hot(hot_max8(acc[0][ut], acc[1][ut]), thr[ut]));
+        any |= hb[ut];
+      }
+      return any;
+    };
+    auto enqueue16 = [&](int t, auto& acc, const uint64_t (&hb)[NT]) {
+      DG_T0(t_e);
+      const int64_t tile0 = i_beg + (int64_t)t * kTileItems;
+      // score_row16(b, kq) = score_row16(b, 0) + 4 kq
+      const uint32_t gbase_q = (uint32_t)(a.item_base + tile0) + 4u * (uint32_t)kq;
+      if (i_end - tile0 < kTileItems) {  // the slice's last tile: as in enqueue()
+        const uint32_t vmask = valid_rows16(i_end - tile0, kq);
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+#pragma unroll
+          for (int ut = 0; ut < NT; ++ut)
+            acc[b >> 2][ut][b & 3] = ((vmask >> b) & 1u) ? acc[b >> 2][ut][b & 3] : -INFINITY;
+      }
+      static_for<0, NT>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        if (hb[j] != 0ull) enqueue_ut(acc, J, gbase_q);
       });
       DG_ADD(kDgEnqueue, t_e);
       DG_CNT(kDgNEnqueue);
@@ -1430,6 +1590,23 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
       if (ntiles > 0) {
         test_job(ntiles - 1, acc1, IC<NU_T - 1>{});
         stage_end_utp();
+      }
+    } else if constexpr (M16) {
+      // the loop below on the 16x16x32 tile: one accumulator set, direct stores
+      dr::f32x4 acc[2][NT];
+      for (int t = 0; t < ntiles; ++t) {
+        DG_CNT(kDgNTiles);
+        if (t % SR == 0) boundary(t / SR);
+        DG_T0(t_m);
+        mma_tile16(t, acc);
+        DG_ADD(kDgMma, t_m);
+        DG_T0(t_h);
+        uint64_t hb[NT];
+        const uint64_t any = any_hits16(acc, hb);
+        DG_ADD(kDgHits, t_h);
+        if (any != 0ull) enqueue16(t, acc, hb);
+        // end of a stage: compact the buffers that passed flush_at
+        if ((t + 1) % SR == 0 || t + 1 == ntiles) check_compact(flush_at, a.slack);
       }
     } else {
     // One accumulator set: the partner wave on the same SIMD issues its MFMAs

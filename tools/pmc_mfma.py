@@ -7,8 +7,9 @@ GRBM_GUI_ACTIVE per dispatch.
         --kernel-ms 1775.0 [--out profiles/pmc_mfma_catalog.json]
 
 Units (MI355X_MICROARCH.md, per-instruction constants): SQ_VALU_MFMA_BUSY_CYCLES
-counts cycles, 32 per v_mfma_f32_32x32x16_bf16 on its SIMD, summed over the
-chip; GRBM_GUI_ACTIVE counts the dispatch's GPU-busy cycles summed over the 8
+counts cycles on the MFMA's SIMD (32 per v_mfma_f32_32x32x16_bf16, 16 per
+v_mfma_f32_16x16x32_bf16 of half the flops: 1024 bf16 flop per cycle for
+either shape), summed over the chip; GRBM_GUI_ACTIVE counts the dispatch's GPU-busy cycles summed over the 8
 XCDs. So a kernel's MFMA utilisation is
 
     mfma_busy_frac = MFMA_BUSY / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs)
@@ -16,7 +17,7 @@ XCDs. So a kernel's MFMA utilisation is
 at the clock the chip held, and its effective clock is GRBM_GUI_ACTIVE / 8 /
 kernel time (--kernel-ms: the kernel-trace average of the same command, from a
 separate unprofiled-counter pass). `expected_busy_from_flops` = flops / 1024
-(2 x 32 x 32 x 16 flop per 32-cycle MFMA) cross-checks the counter against the
+(1024 flop per MFMA cycle, both bf16 shapes) cross-checks the counter against the
 algorithmic flops of the launch (--flops, for the kernel named by --flops-kernel).
 """
 import argparse
