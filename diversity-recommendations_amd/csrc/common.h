@@ -57,6 +57,29 @@ __device__ __forceinline__ float bf16_bits_to_f32(uint32_t b16) {
   return __uint_as_float(b16 << 16);
 }
 
+// LDS written by the lanes of a wave is visible to its other lanes after this
+// (one wave's private LDS area: no workgroup barrier).
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// v_mfma_f32_32x32x16: accumulator register q of a lane of half-wave h
+// (lane >> 5) holds row tile_row(q, h) of column (lane & 31).
+__host__ __device__ constexpr int tile_row(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
+
+// LDS image of rows of D bf16: the 16-B chunk c of row r sits at chunk
+// c ^ swz(r), which spreads the 32 rows that one A-fragment ds_read_b128
+// touches over distinct 16-B bank slots.
+template <int D>
+struct RowSwizzle {
+  static constexpr int CPR = D / 8;                               // 16-B chunks per row
+  static constexpr int RPB = (2 * D >= 256) ? 1 : 256 / (2 * D);  // rows per 256-B bank row
+  static constexpr int SWM = (CPR < 16 ? CPR : 16) - 1;
+  __host__ __device__ static constexpr int swz(int r) { return (r / RPB) & SWM; }
+};
+
 // ---------------------------------------------------------------- top-K keys
 // A (score, item) pair is packed into one 64-bit key whose unsigned order is
 // the ranking order of the reference path with its tie-break made explicit:

@@ -31,6 +31,33 @@ __device__ __forceinline__ int64_t rec_at(const R* recs, int64_t i) {
   return (int64_t)recs[i];
 }
 
+// Host side: a runtime value picks a template argument. for_int<Vs...>(v, f)
+// calls f(std::integral_constant<int, V>{}) for the V that equals v and says
+// whether there was one (the launchers pass that on: no match is an error,
+// not a launch that never happened); with_recs hands f the typed list pointer.
+template <int... Vs, class F>
+bool for_int(int v, F&& f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+template <class F>
+bool for_kind(int kind, F&& f) {
+  return for_int<DR_ILD_COSINE, DR_ILD_DOT, DR_ILD_EUCLIDEAN>(kind, f);
+}
+template <class F>
+bool for_tiles(int k, F&& f) {  // NT row tiles of 32, k <= 128
+  return for_int<1, 2, 3, 4>((k + 31) / 32, f);
+}
+template <class F>
+bool for_kind_tiles(int kind, int k, F&& f) {  // f(KIND, NT); false when either has no match
+  bool ran = false;
+  for_kind(kind, [&](auto KIND) { ran = for_tiles(k, [&](auto NT) { f(KIND, NT); }); });
+  return ran;
+}
+template <class F>
+auto with_recs(const void* recs, int rec_dtype, F&& f) {
+  return rec_dtype == DR_I32 ? f((const int32_t*)recs) : f((const int64_t*)recs);
+}
+
 // Id range check of one list (include/divrec_hip.h): true when every id is in
 // [0, n_items). Wave-wide (every lane gets the answer); the one-lane form
 // below serves the one-lane-per-user kernel.
@@ -52,6 +79,13 @@ __device__ __forceinline__ bool lane_list_ok(const R* r, int k, int64_t n_items)
   }
   return !bad;
 }
+// What a list that fails the check gets, from the one lane that reports it:
+// NaN for its user (in raw where the pair sum was asked for) and one count.
+__device__ __forceinline__ void flag_bad_list(int64_t u, float* out, double* raw, int32_t* err) {
+  if (raw) raw[u] = __builtin_nan("");
+  else out[u] = __builtin_nanf("");
+  if (err) atomicAdd(err, 1);
+}
 
 // --------------------------------------------------------------- dense, float
 template <typename R, typename T, typename ACC>
@@ -63,12 +97,7 @@ __global__ __launch_bounds__(256) void ild_dense_seq(const R* __restrict__ recs,
   const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (u >= n_users) return;
   const R* r = recs + u * k;
-  if (!lane_list_ok(r, k, n_items)) {
-    if (raw) raw[u] = __builtin_nan("");
-    else out[u] = __builtin_nanf("");
-    if (err) atomicAdd(err, 1);
-    return;
-  }
+  if (!lane_list_ok(r, k, n_items)) return flag_bad_list(u, out, raw, err);
   ACC acc = 0;
   for (int p = 0; p < k; ++p) {
     const T* row = D + rec_at(r, p) * n_items;
@@ -90,11 +119,7 @@ __global__ __launch_bounds__(256) void ild_dense_int(const R* __restrict__ recs,
   if (u >= n_users) return;
   const R* r = recs + u * k;
   if (!wave_list_ok(r, k, n_items)) {  // wave-uniform
-    if (lane == 0) {
-      if (raw) raw[u] = __builtin_nan("");
-      else out[u] = __builtin_nanf("");
-      if (err) atomicAdd(err, 1);
-    }
+    if (lane == 0) flag_bad_list(u, out, raw, err);
     return;
   }
   long long acc = 0;
@@ -111,85 +136,70 @@ __global__ __launch_bounds__(256) void ild_dense_int(const R* __restrict__ recs,
 }
 
 // --------------------------------------------------------------- labels
+// One wave per user. STAGED: the list's labels are staged in LDS (k <=
+// kLabelMaxK); longer lists (the reference's user_ild takes any length,
+// intra_list_diversity_score.py:36-42) read them through the cache. The
+// count is exact either way.
 constexpr int kLabelMaxK = 1024;
-template <typename R>
+template <typename R, bool STAGED>
 __global__ __launch_bounds__(256) void ild_labels_kernel(const R* __restrict__ recs,
                                                          int64_t n_users, int k,
                                                          const int64_t* __restrict__ labels,
                                                          int64_t n_items, float* __restrict__ out,
                                                          int32_t* __restrict__ err) {
-  __shared__ int64_t s_lab[4][kLabelMaxK];
   const int lane = dr::lane_id();
-  const int wave = threadIdx.x >> 6;
   const int64_t u = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
   if (u >= n_users) return;  // wave-uniform; no block barrier below
   const R* r = recs + u * k;
   if (!wave_list_ok(r, k, n_items)) {  // wave-uniform
-    if (lane == 0) {
-      out[u] = __builtin_nanf("");
-      if (err) atomicAdd(err, 1);
-    }
+    if (lane == 0) flag_bad_list(u, out, nullptr, err);
     return;
   }
-  int64_t* lab = s_lab[wave];
-  for (int p = lane; p < k; p += 64) lab[p] = labels[rec_at(r, p)];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int64_t* lab = nullptr;  // the wave's staged labels
+  if constexpr (STAGED) {
+    __shared__ int64_t s_lab[4][kLabelMaxK];
+    int64_t* mine = s_lab[threadIdx.x >> 6];
+    for (int p = lane; p < k; p += 64) mine[p] = labels[rec_at(r, p)];
+    dr::wave_lds_sync();
+    lab = mine;
+  }
+  auto label_at = [&](int p) -> int64_t { return STAGED ? lab[p] : labels[rec_at(r, p)]; };
   long long cnt = 0;
   for (int p = lane; p < k; p += 64) {
-    const int64_t lp = lab[p];
-    for (int q = p + 1; q < k; ++q) cnt += (lab[q] == lp);
+    const int64_t lp = label_at(p);
+    for (int q = p + 1; q < k; ++q) cnt += (label_at(q) == lp);
   }
 #pragma unroll
   for (int m = 32; m > 0; m >>= 1) cnt += __shfl_xor(cnt, m);
-  if (lane == 0) out[u] = (float)cnt / (float)(k * (k - 1));
-}
-
-// Lists longer than the LDS staging area (the reference's user_ild takes any
-// length, intra_list_diversity_score.py:36-42): the same exact count with the
-// labels read through the cache; one wave per user.
-template <typename R>
-__global__ __launch_bounds__(256) void ild_labels_long_kernel(const R* __restrict__ recs,
-                                                              int64_t n_users, int k,
-                                                              const int64_t* __restrict__ labels,
-                                                              int64_t n_items,
-                                                              float* __restrict__ out,
-                                                              int32_t* __restrict__ err) {
-  const int lane = dr::lane_id();
-  const int64_t u = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-  if (u >= n_users) return;  // wave-uniform
-  const R* r = recs + u * k;
-  if (!wave_list_ok(r, k, n_items)) {  // wave-uniform
-    if (lane == 0) {
-      out[u] = __builtin_nanf("");
-      if (err) atomicAdd(err, 1);
-    }
-    return;
-  }
-  long long cnt = 0;
-  for (int p = lane; p < k; p += 64) {
-    const int64_t lp = labels[rec_at(r, p)];
-    for (int q = p + 1; q < k; ++q) cnt += (labels[rec_at(r, q)] == lp);
-  }
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) cnt += __shfl_xor(cnt, m);
-  if (lane == 0) out[u] = (float)cnt / (float)((long long)k * (k - 1));  // as the short kernel
+  if (lane == 0) out[u] = (float)cnt / (float)((long long)k * (k - 1));
 }
 
 // --------------------------------------------------------------- embeddings
 // One wave per user. Tile t holds rows [32t, 32t+32) of the user's list as
 // MFMA fragments: lane l -> row (l & 31), k-slice 8*(l >> 5) + 16*s. The same
 // fragment serves as A (rows) and B (columns) operand of X * X^T.
+
+// The list position whose row this lane gathers for tile t (positions past
+// the list repeat its first row; the pair masks leave them out).
+__device__ __forceinline__ int tile_pos(int t, int col, int k) {
+  const int p = 32 * t + col;
+  return p < k ? p : 0;
+}
+// This lane's fragments of table row `row` (h = lane >> 5, col = lane & 31
+// throughout).
+template <int D>
+__device__ __forceinline__ void gather_row(const __bf16* __restrict__ E, int64_t row, int h,
+                                           bf16x8 (&f)[D / 16]) {
+  const uint4* src = reinterpret_cast<const uint4*>(E + row * D + 8 * h);
+#pragma unroll
+  for (int s = 0; s < D / 16; ++s) f[s] = __builtin_bit_cast(bf16x8, src[2 * s]);
+}
+// Tile t of a list whose row ids sit in LDS (the d = 256 kernel).
 template <int D>
 __device__ __forceinline__ void load_tile(const __bf16* __restrict__ E, const int64_t* rows,
                                           int t, int k, bf16x8 (&f)[D / 16]) {
   const int lane = dr::lane_id();
-  const int p = 32 * t + (lane & 31);
-  const int64_t row = rows[p < k ? p : 0];
-  const uint4* src = reinterpret_cast<const uint4*>(E + row * D + 8 * (lane >> 5));
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) f[s] = __builtin_bit_cast(bf16x8, src[2 * s]);
+  gather_row<D>(E, rows[tile_pos(t, lane & 31, k)], lane >> 5, f);
 }
 
 template <int D>
@@ -216,6 +226,34 @@ __device__ __forceinline__ f32x16 gram_tile_after(const bf16x8 (&x)[D / 16],
   return acc;
 }
 
+// Element (c, c) of a Gram tile is register diag_reg(c) of the lane with
+// col = c in the half-wave that diag_owner(col, h) is true for.
+__device__ constexpr int diag_reg(int col) { return (col & 3) + 4 * (col >> 3); }
+__device__ __forceinline__ bool diag_owner(int col, int h) { return ((col >> 2) & 1) == h; }
+
+// Distance of a pair from its Gram element g and the per-row terms of its two
+// rows: 1/|e| (cosine), unused (dot), |e|^2 (euclidean).
+template <int KIND>
+__device__ __forceinline__ float pair_dist(float g, float wi, float wj) {
+  if constexpr (KIND == DR_ILD_COSINE) return fmaf(-g, wi * wj, 1.f);
+  else if constexpr (KIND == DR_ILD_DOT) return g;
+  else return sqrtf(fmaxf(wi + wj - 2.f * g, 0.f));
+}
+// Register q of one Gram tile in the pair sum: the distance of column j (jv:
+// inside the list) and row i0 + tile_row(q, h), whose term is wi[q], or 0 for
+// a pair that does not count; a diagonal tile keeps its strict upper
+// triangle (i0 and j from any common origin: list positions, or 0 and col).
+// The callers add the 16 terms in register order themselves (added in here,
+// the adds reach them commuted: another instruction stream).
+template <int KIND>
+__device__ __forceinline__ float pair_term(int q, const f32x16& g, const float (&wi)[16],
+                                           float wj, bool jv, bool offdiag, int i0, int j,
+                                           int h) {
+  const bool ok = jv && (offdiag || i0 + dr::tile_row(q, h) < j);
+  const float dist = pair_dist<KIND>(g[q], wi[q], wj);
+  return ok ? dist : 0.f;
+}
+
 constexpr int kEmbMaxK = 128;
 
 template <typename R, int D>
@@ -234,35 +272,30 @@ __global__ __launch_bounds__(256) void ild_embedding_kernel(const R* __restrict_
   if (u >= n_users) return;  // wave-uniform
   const R* r = recs + u * k;
   if (!wave_list_ok(r, k, n_items)) {  // wave-uniform
-    if (lane == 0) {
-      out[u] = __builtin_nanf("");
-      if (err) atomicAdd(err, 1);
-    }
+    if (lane == 0) flag_bad_list(u, out, nullptr, err);
     return;
   }
   int64_t* rows = s_rows[wave];
   float* nsq = s_nsq[wave];
   for (int p = lane; p < k; p += 64) rows[p] = rec_at(r, p);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  dr::wave_lds_sync();
   const int nt = (k + 31) / 32;
 
-  // Squared norms from the diagonal tiles: element (row == col) sits in the
-  // lane with col = j and register r = (j & 3) + 4 * (j >> 3) when (j >> 2) & 1 == h.
+  // Squared norms from the diagonal tiles (the select chain written out as in
+  // ild_embedding_regs, which says why). Further down this kernel's dot /
+  // euclidean distances are written out too: with pair_dist its instruction
+  // stream changes (profiles/ild_dedupe/).
   for (int t = 0; t < nt; ++t) {
     bf16x8 x[D / 16];
     load_tile<D>(E, rows, t, k, x);
     const f32x16 g = gram_tile<D>(x, x);
-    const int ri = (col & 3) + 4 * (col >> 3);
+    const int ri = diag_reg(col);
     float v = g[0];
 #pragma unroll
     for (int q = 1; q < 16; ++q) v = (ri == q) ? g[q] : v;
-    if (((col >> 2) & 1) == h) nsq[32 * t + col] = v;
+    if (diag_owner(col, h)) nsq[32 * t + col] = v;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  dr::wave_lds_sync();
 
   float sum = 0.f;
   for (int ti = 0; ti < nt; ++ti) {
@@ -276,9 +309,10 @@ __global__ __launch_bounds__(256) void ild_embedding_kernel(const R* __restrict_
       const float nj = j < k ? nsq[j] : 1.f;
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const int i = 32 * ti + (q & 3) + 8 * (q >> 2) + 4 * h;
+        const int i = 32 * ti + dr::tile_row(q, h);
         if (i < j && j < k) {
           const float ni = nsq[i];
+          // cosine from the squared norms (the kernels below keep 1/|e| per row)
           float dist;
           if (kind == DR_ILD_COSINE) dist = 1.f - g[q] / (sqrtf(ni) * sqrtf(nj));
           else if (kind == DR_ILD_DOT) dist = g[q];
@@ -316,31 +350,24 @@ __global__ __launch_bounds__(64) void ild_embedding_long(const R* __restrict__ r
   const int64_t u = blockIdx.x;
   const R* r = recs + u * k;
   if (!wave_list_ok(r, k, n_items)) {  // wave-uniform
-    if (lane == 0) {
-      out[u] = __builtin_nanf("");
-      if (err) atomicAdd(err, 1);
-    }
+    if (lane == 0) flag_bad_list(u, out, nullptr, err);
     return;
   }
   const int nt = (k + 31) / 32;
   auto load = [&](int t, bf16x8 (&f)[KS]) {
-    const int p = 32 * t + col;
-    const int64_t row = rec_at(r, p < k ? p : 0);
-    const uint4* src = reinterpret_cast<const uint4*>(E + row * D + 8 * h);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) f[s] = __builtin_bit_cast(bf16x8, src[2 * s]);
+    gather_row<D>(E, rec_at(r, tile_pos(t, col, k)), h, f);
   };
   if constexpr (KIND != DR_ILD_DOT) {
     for (int t = 0; t < nt; ++t) {
       bf16x8 x[KS];
       load(t, x);
       const f32x16 g = gram_tile<D>(x, x);
-      const int ri = (col & 3) + 4 * (col >> 3);
+      const int ri = diag_reg(col);
       float v = g[0];
 #pragma unroll
       for (int q = 1; q < 16; ++q) v = (ri == q) ? g[q] : v;
       if (KIND == DR_ILD_COSINE) v = 1.f / sqrtf(v);
-      if (((col >> 2) & 1) == h && 32 * t + col < k) s_w[32 * t + col] = v;
+      if (diag_owner(col, h) && 32 * t + col < k) s_w[32 * t + col] = v;
     }
     __syncthreads();
   }
@@ -351,7 +378,7 @@ __global__ __launch_bounds__(64) void ild_embedding_long(const R* __restrict__ r
     float wi[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int i = 32 * ti + (q & 3) + 8 * (q >> 2) + 4 * h;
+      const int i = 32 * ti + dr::tile_row(q, h);
       wi[q] = (KIND != DR_ILD_DOT && i < k) ? s_w[i] : 0.f;
     }
     for (int tj = ti; tj < nt; ++tj) {
@@ -364,12 +391,13 @@ __global__ __launch_bounds__(64) void ild_embedding_long(const R* __restrict__ r
       float part = 0.f;  // <= 16 terms in fp32, the tile sums in double
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
+        // pair_term's mask with the row map dr::tile_row(q, h) written out:
+        // with either call in this loop the kernel's instruction stream
+        // changes (a build with pair_term here measured 3-4 % slower at
+        // d = 128, k = 300: profiles/ild_dedupe/)
         const int i = 32 * ti + (q & 3) + 8 * (q >> 2) + 4 * h;
         const bool ok = jv && (ti < tj || i < j);
-        float dist;
-        if constexpr (KIND == DR_ILD_COSINE) dist = fmaf(-g[q], wi[q] * wj, 1.f);
-        else if constexpr (KIND == DR_ILD_DOT) dist = g[q];
-        else dist = sqrtf(fmaxf(wi[q] + wj - 2.f * g[q], 0.f));
+        const float dist = pair_dist<KIND>(g[q], wi[q], wj);
         part += ok ? dist : 0.f;
       }
       sum += (double)part;
@@ -381,16 +409,14 @@ __global__ __launch_bounds__(64) void ild_embedding_long(const R* __restrict__ r
 }
 
 template <typename R, int D>
-void launch_long(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t ni, int kind,
+bool launch_long(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t ni, int kind,
                  float* out, int32_t* err, hipStream_t s) {
-  const dim3 grid((unsigned)n_users);
-  const size_t lds = (size_t)k * sizeof(float);  // k <= kEmbLongMaxK: at most 64 KB
-  if (kind == DR_ILD_COSINE)
-    hipLaunchKernelGGL((ild_embedding_long<R, D, DR_ILD_COSINE>), grid, 64, lds, s, recs, n_users, k, E, ni, out, err);
-  else if (kind == DR_ILD_DOT)
-    hipLaunchKernelGGL((ild_embedding_long<R, D, DR_ILD_DOT>), grid, 64, 0, s, recs, n_users, k, E, ni, out, err);
-  else
-    hipLaunchKernelGGL((ild_embedding_long<R, D, DR_ILD_EUCLIDEAN>), grid, 64, lds, s, recs, n_users, k, E, ni, out, err);
+  return for_kind(kind, [&](auto KIND) {
+    // k <= kEmbLongMaxK: at most 64 KB
+    const size_t lds = KIND == DR_ILD_DOT ? 0 : (size_t)k * sizeof(float);
+    hipLaunchKernelGGL((ild_embedding_long<R, D, KIND>), dim3((unsigned)n_users), 64, lds, s, recs,
+                       n_users, k, E, ni, out, err);
+  });
 }
 
 // Register-resident variant for nt = NT row tiles: every row of the list is
@@ -419,36 +445,27 @@ __global__ __launch_bounds__(256, 2) void ild_embedding_regs(const R* __restrict
   if (u >= n_users) return;  // wave-uniform
   const R* r = recs + u * k;
   if (!wave_list_ok(r, k, n_items)) {  // wave-uniform
-    if (lane == 0) {
-      out[u] = __builtin_nanf("");
-      if (err) atomicAdd(err, 1);
-    }
+    if (lane == 0) flag_bad_list(u, out, nullptr, err);
     return;
   }
   float* w = s_w[wave];
   bf16x8 x[NT][KS];
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int p = 32 * t + col;
-    const int64_t row = rec_at(r, p < k ? p : 0);
-    const uint4* src = reinterpret_cast<const uint4*>(E + row * D + 8 * h);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) x[t][s] = __builtin_bit_cast(bf16x8, src[2 * s]);
-  }
+  for (int t = 0; t < NT; ++t) gather_row<D>(E, rec_at(r, tile_pos(t, col, k)), h, x[t]);
   if constexpr (KIND != DR_ILD_DOT) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
+      // the diagonal's select chain written out: as a function (with the
+      // 1/sqrt) it changes this kernel's instruction stream (profiles/ild_dedupe/)
       const f32x16 g = gram_tile<D>(x[t], x[t]);
-      const int ri = (col & 3) + 4 * (col >> 3);
+      const int ri = diag_reg(col);
       float v = g[0];
 #pragma unroll
       for (int q = 1; q < 16; ++q) v = (ri == q) ? g[q] : v;
       if (KIND == DR_ILD_COSINE) v = 1.f / sqrtf(v);
-      if (((col >> 2) & 1) == h) w[32 * t + col] = v;
+      if (diag_owner(col, h)) w[32 * t + col] = v;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    dr::wave_lds_sync();
   }
   float sum = 0.f;
 #pragma unroll
@@ -456,7 +473,7 @@ __global__ __launch_bounds__(256, 2) void ild_embedding_regs(const R* __restrict
     float wi[16];
     if constexpr (KIND != DR_ILD_DOT) {
 #pragma unroll
-      for (int q = 0; q < 16; ++q) wi[q] = w[32 * ti + (q & 3) + 8 * (q >> 2) + 4 * h];
+      for (int q = 0; q < 16; ++q) wi[q] = w[32 * ti + dr::tile_row(q, h)];
     }
 #pragma unroll
     for (int tj = ti; tj < NT; ++tj) {
@@ -467,38 +484,20 @@ __global__ __launch_bounds__(256, 2) void ild_embedding_regs(const R* __restrict
       const bool jv = j < k;
       const float wj = (KIND != DR_ILD_DOT && jv) ? w[j] : 0.f;
 #pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int i = 32 * ti + (q & 3) + 8 * (q >> 2) + 4 * h;
-        const bool ok = jv && (ti < tj || i < j);
-        float dist;
-        if constexpr (KIND == DR_ILD_COSINE) dist = fmaf(-g[q], wi[q] * wj, 1.f);
-        else if constexpr (KIND == DR_ILD_DOT) dist = g[q];
-        else dist = sqrtf(fmaxf(wi[q] + wj - 2.f * g[q], 0.f));
-        sum += ok ? dist : 0.f;
-      }
+      for (int q = 0; q < 16; ++q) sum += pair_term<KIND>(q, g, wi, wj, jv, ti < tj, 32 * ti, j, h);
     }
   }
   sum = dr::wave_sum_f32(sum);
   if (lane == 0) out[u] = sum / (float)(k * (k - 1));
 }
 
-template <typename R, int D, int KIND>
-void launch_regs_kind(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t ni,
-                      float* out, int32_t* err, hipStream_t s, int grid) {
-  switch ((k + 31) / 32) {
-    case 1: hipLaunchKernelGGL((ild_embedding_regs<R, D, 1, KIND>), grid, 256, 0, s, recs, n_users, k, E, ni, out, err); break;
-    case 2: hipLaunchKernelGGL((ild_embedding_regs<R, D, 2, KIND>), grid, 256, 0, s, recs, n_users, k, E, ni, out, err); break;
-    case 3: hipLaunchKernelGGL((ild_embedding_regs<R, D, 3, KIND>), grid, 256, 0, s, recs, n_users, k, E, ni, out, err); break;
-    default: hipLaunchKernelGGL((ild_embedding_regs<R, D, 4, KIND>), grid, 256, 0, s, recs, n_users, k, E, ni, out, err); break;
-  }
-}
-
 template <typename R, int D>
-void launch_regs(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t ni, int kind,
+bool launch_regs(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t ni, int kind,
                  float* out, int32_t* err, hipStream_t s, int grid) {
-  if (kind == DR_ILD_COSINE) launch_regs_kind<R, D, DR_ILD_COSINE>(recs, n_users, k, E, ni, out, err, s, grid);
-  else if (kind == DR_ILD_DOT) launch_regs_kind<R, D, DR_ILD_DOT>(recs, n_users, k, E, ni, out, err, s, grid);
-  else launch_regs_kind<R, D, DR_ILD_EUCLIDEAN>(recs, n_users, k, E, ni, out, err, s, grid);
+  return for_kind_tiles(kind, k, [&](auto KIND, auto NT) {
+    hipLaunchKernelGGL((ild_embedding_regs<R, D, NT, KIND>), grid, 256, 0, s, recs, n_users, k, E,
+                       ni, out, err);
+  });
 }
 
 // ------------------------------------------------------ embeddings, streamed
@@ -600,10 +599,9 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
     const R* __restrict__ recs, int64_t n_users, int k, const __bf16* __restrict__ E,
     int64_t n_items, float* __restrict__ out, int32_t* __restrict__ err, StreamShape sh) {
   constexpr int KS = D / 16;
-  constexpr int CPR = D / 8;                               // 16-B chunks per row
-  constexpr int RPI = 64 / CPR;                            // rows per 1-KB piece
-  constexpr int RPB = (2 * D >= 256) ? 1 : 256 / (2 * D);  // rows per 256-B bank row
-  constexpr int SWM = (CPR < 16 ? CPR : 16) - 1;
+  using SW = dr::RowSwizzle<D>;  // the image's swizzle (the score scan's)
+  constexpr int CPR = SW::CPR;   // 16-B chunks per row
+  constexpr int RPI = 64 / CPR;  // rows per 1-KB piece
   __shared__ __attribute__((aligned(16))) char smem[kStreamLds];
   const int lane = dr::lane_id();
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -666,7 +664,7 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
         const int j = j0 + jj;
         if (j >= ni) break;
         const uint64_t id = (idv[jj] >= 0 && idv[jj] < n_items) ? (uint64_t)idv[jj] : 0ull;
-        const int lc = (lane % CPR) ^ (((j * RPI + gq) / RPB) & SWM);
+        const int lc = (lane % CPR) ^ SW::swz(j * RPI + gq);
         const char* src = Eb + id * (uint64_t)(2 * D) + lc * 16;
         const uint32_t m0 = __builtin_amdgcn_readfirstlane(dst + 1024u * (uint32_t)j);
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
@@ -676,15 +674,14 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
   };
 
   // per-lane constants of the Gram epilogue: register q of a 32x32 tile holds
-  // row i(q) = (q & 3) + 8 (q >> 2) + 4 h of column col
+  // row i(q) = dr::tile_row(q, h) of column col
   f2 onehot[8], upper[8];  // q == the diagonal's register; i(q) < col
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int q0 = 2 * q, q1 = 2 * q + 1;
-    const int ri = (col & 3) + 4 * (col >> 3);
+    const int ri = diag_reg(col);
     onehot[q] = f2{ri == q0 ? 1.f : 0.f, ri == q1 ? 1.f : 0.f};
-    upper[q] = f2{(q0 & 3) + 8 * (q0 >> 2) + 4 * h < col ? 1.f : 0.f,
-                  (q1 & 3) + 8 * (q1 >> 2) + 4 * h < col ? 1.f : 0.f};
+    upper[q] = f2{dr::tile_row(q0, h) < col ? 1.f : 0.f, dr::tile_row(q1, h) < col ? 1.f : 0.f};
   }
   // prologue: the lists of users 0..nb-1, then (in the loop's issue order)
   // list(m + nb) + rows(m) for m < nb
@@ -715,7 +712,7 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
     for (int t = 0; t < NT; ++t) {
       const int rr = 32 * t + col < k ? 32 * t + col : k - 1;
       const char* row = img + rr * (2 * D);
-      const int sw = (rr / RPB) & SWM;
+      const int sw = SW::swz(rr);
 #pragma unroll
       for (int s = 0; s < KS; ++s)
         x[t][s] = *reinterpret_cast<const bf16x8*>(row + (((2 * s + h) ^ sw) << 4));
@@ -747,13 +744,11 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
       float v = dv.x + dv.y;
       if constexpr (KIND == DR_ILD_COSINE) v = __builtin_amdgcn_rsqf(v);  // <= 1 ulp
       else if constexpr (KIND == DR_ILD_DOT) v = 1.f;
-      if (((col >> 2) & 1) == h) w[32 * t + col] = 32 * t + col < k ? v : 0.f;
+      if (diag_owner(col, h)) w[32 * t + col] = 32 * t + col < k ? v : 0.f;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // the 16 rows of a lane's accumulator: i = (q & 3) + 8 (q >> 2) + 4 h, so
-    // rows 8m + 4h .. +3 are registers 4m .. 4m + 3 (one ds_read_b128 each)
+    dr::wave_lds_sync();
+    // the 16 rows of a lane's accumulator (dr::tile_row): rows 8m + 4h .. +3
+    // are registers 4m .. 4m + 3 (one ds_read_b128 each)
     auto row_terms = [&](int t, float (&wi)[16]) {
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
@@ -802,14 +797,9 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
           const f32x16 g = tile_of(ti, tj);
           const int j = 32 * tj + col;
           const bool jv = j < k;
-          const float wj = w[j];
 #pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const int i = 32 * ti + (q & 3) + 8 * (q >> 2) + 4 * h;
-            const bool ok = jv && (ti < tj || i < j);
-            const float dist = sqrtf(fmaxf(wi[q] + wj - 2.f * g[q], 0.f));
-            sum += ok ? dist : 0.f;
-          }
+          for (int q = 0; q < 16; ++q)
+            sum += pair_term<KIND>(q, g, wi, w[j], jv, ti < tj, 32 * ti, j, h);
         }
       }
       sum = wave_sum_dpp(sum);
@@ -825,9 +815,7 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
       ++nbad;
     }
     // w is rewritten by the next user's norms only after every lane read it
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    dr::wave_lds_sync();
     if (lane == 0)
       asm volatile("global_store_dword %0, %1, off" : : "v"(out + user_of(n)), "v"(res) : "memory");
     ILD_ADD(3, t_t);
@@ -844,43 +832,39 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
   if (nbad && err && lane == 0) atomicAdd(err, nbad);
 }
 
-template <typename R, int D, int KIND>
-void launch_stream_kind(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t ni,
-                        float* out, int32_t* err, hipStream_t s, const StreamShape& sh, int grid) {
-  switch ((k + 31) / 32) {
-    case 1: hipLaunchKernelGGL((ild_embedding_stream<R, D, 1, KIND>), grid, kStreamWaves * 64, 0, s, recs, n_users, k, E, ni, out, err, sh); break;
-    case 2: hipLaunchKernelGGL((ild_embedding_stream<R, D, 2, KIND>), grid, kStreamWaves * 64, 0, s, recs, n_users, k, E, ni, out, err, sh); break;
-    case 3: hipLaunchKernelGGL((ild_embedding_stream<R, D, 3, KIND>), grid, kStreamWaves * 64, 0, s, recs, n_users, k, E, ni, out, err, sh); break;
-    default: hipLaunchKernelGGL((ild_embedding_stream<R, D, 4, KIND>), grid, kStreamWaves * 64, 0, s, recs, n_users, k, E, ni, out, err, sh); break;
-  }
-}
-
 template <typename R, int D>
-void launch_stream(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t ni, int kind,
+bool launch_stream(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t ni, int kind,
                    float* out, int32_t* err, hipStream_t s) {
   const StreamShape sh = stream_shape(k, D, (int)sizeof(R));
   const int64_t need = dr::ceil_div(n_users, kStreamWaves);  // a wave per user at most
   const int cus = dr::device_cus();
   const int grid = (int)(need < cus ? need : cus);
-  if (kind == DR_ILD_COSINE) launch_stream_kind<R, D, DR_ILD_COSINE>(recs, n_users, k, E, ni, out, err, s, sh, grid);
-  else if (kind == DR_ILD_DOT) launch_stream_kind<R, D, DR_ILD_DOT>(recs, n_users, k, E, ni, out, err, s, sh, grid);
-  else launch_stream_kind<R, D, DR_ILD_EUCLIDEAN>(recs, n_users, k, E, ni, out, err, s, sh, grid);
+  return for_kind_tiles(kind, k, [&](auto KIND, auto NT) {
+    hipLaunchKernelGGL((ild_embedding_stream<R, D, NT, KIND>), grid, kStreamWaves * 64, 0, s, recs,
+                       n_users, k, E, ni, out, err, sh);
+  });
 }
 
 template <typename R>
 int launch_embedding(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t ni, int d,
                      int kind, float* out, int32_t* err, hipStream_t s) {
   const int grid = (int)dr::ceil_div(n_users, 4);
+  const auto bad_width = [] {
+    dr::set_error("dr_ild_embedding: d must be one of 32, 64, 128, 256");
+    return DR_EUNSUPPORTED;
+  };
+  // a width that matched but a kind or tile count without a kernel (the entry
+  // point validates both, so unreachable): an error, never a silent no-op
+  const auto no_kernel = [] {
+    dr::set_error("dr_ild_embedding: no kernel for this kind and k");
+    return DR_EINVAL;
+  };
+  bool launched = false;
   if (k > kEmbMaxK) {  // long lists: the streaming kernel, any width
-    switch (d) {
-      case 32: launch_long<R, 32>(recs, n_users, k, E, ni, kind, out, err, s); return DR_OK;
-      case 64: launch_long<R, 64>(recs, n_users, k, E, ni, kind, out, err, s); return DR_OK;
-      case 128: launch_long<R, 128>(recs, n_users, k, E, ni, kind, out, err, s); return DR_OK;
-      case 256: launch_long<R, 256>(recs, n_users, k, E, ni, kind, out, err, s); return DR_OK;
-      default:
-        dr::set_error("dr_ild_embedding: d must be one of 32, 64, 128, 256");
-        return DR_EUNSUPPORTED;
-    }
+    const bool ok = for_int<32, 64, 128, 256>(d, [&](auto D) {
+      launched = launch_long<R, D>(recs, n_users, k, E, ni, kind, out, err, s);
+    });
+    return !ok ? bad_width() : launched ? DR_OK : no_kernel();
   }
   // the whole list fits in registers for d <= 128 (k <= 128 = 4 tiles).
   // Streamed where it wins (profiles/r06/ild_ab/, 1M users over 10M rows):
@@ -895,55 +879,29 @@ int launch_embedding(const R* recs, int64_t n_users, int k, const __bf16* E, int
   const bool stream = dr::plan_knob(DR_KNOB_ILD_STREAM, &sv)
                           ? sv != 0.0
                           : d == 128 && kind != DR_ILD_EUCLIDEAN && k > kStreamMinK;
-  if (stream && (d == 32 || d == 64 || d == 128)) {
-    if (d == 32) launch_stream<R, 32>(recs, n_users, k, E, ni, kind, out, err, s);
-    else if (d == 64) launch_stream<R, 64>(recs, n_users, k, E, ni, kind, out, err, s);
-    else launch_stream<R, 128>(recs, n_users, k, E, ni, kind, out, err, s);
-    return DR_OK;
-  }
-  if (d == 32 || d == 64 || d == 128) {
-    if (d == 32) launch_regs<R, 32>(recs, n_users, k, E, ni, kind, out, err, s, grid);
-    else if (d == 64) launch_regs<R, 64>(recs, n_users, k, E, ni, kind, out, err, s, grid);
-    else launch_regs<R, 128>(recs, n_users, k, E, ni, kind, out, err, s, grid);
-    return DR_OK;
-  }
-  switch (d) {
-    case 256: hipLaunchKernelGGL((ild_embedding_kernel<R, 256>), grid, 256, 0, s, recs, n_users, k, E, ni, kind, out, err); break;
-    default:
-      dr::set_error("dr_ild_embedding: d must be one of 32, 64, 128, 256");
-      return DR_EUNSUPPORTED;
-  }
+  const bool ok = for_int<32, 64, 128>(d, [&](auto D) {
+    launched = stream ? launch_stream<R, D>(recs, n_users, k, E, ni, kind, out, err, s)
+                      : launch_regs<R, D>(recs, n_users, k, E, ni, kind, out, err, s, grid);
+  });
+  if (ok) return launched ? DR_OK : no_kernel();
+  if (d != 256) return bad_width();
+  hipLaunchKernelGGL((ild_embedding_kernel<R, 256>), grid, 256, 0, s, recs, n_users, k, E, ni, kind,
+                     out, err);
   return DR_OK;
 }
 
 template <typename R>
 int launch_dense(const R* recs, int64_t n_users, int k, const void* D, int dd, int64_t n_items,
                  float* out, double* raw, int32_t* err, hipStream_t s) {
+  const auto go = [&](auto kernel, int users_per_block, auto* dist) {
+    const int grid = (int)dr::ceil_div(n_users, users_per_block);
+    hipLaunchKernelGGL(kernel, grid, 256, 0, s, recs, n_users, k, dist, n_items, out, raw, err);
+  };
   switch (dd) {
-    case DR_F32: {
-      const int grid = (int)dr::ceil_div(n_users, 256);
-      hipLaunchKernelGGL((ild_dense_seq<R, float, float>), grid, 256, 0, s, recs, n_users, k,
-                         (const float*)D, n_items, out, raw, err);
-      break;
-    }
-    case DR_F64: {
-      const int grid = (int)dr::ceil_div(n_users, 256);
-      hipLaunchKernelGGL((ild_dense_seq<R, double, double>), grid, 256, 0, s, recs, n_users, k,
-                         (const double*)D, n_items, out, raw, err);
-      break;
-    }
-    case DR_I32: {
-      const int grid = (int)dr::ceil_div(n_users, 4);
-      hipLaunchKernelGGL((ild_dense_int<R, int32_t>), grid, 256, 0, s, recs, n_users, k,
-                         (const int32_t*)D, n_items, out, raw, err);
-      break;
-    }
-    case DR_I64: {
-      const int grid = (int)dr::ceil_div(n_users, 4);
-      hipLaunchKernelGGL((ild_dense_int<R, int64_t>), grid, 256, 0, s, recs, n_users, k,
-                         (const int64_t*)D, n_items, out, raw, err);
-      break;
-    }
+    case DR_F32: go(ild_dense_seq<R, float, float>, 256, (const float*)D); break;
+    case DR_F64: go(ild_dense_seq<R, double, double>, 256, (const double*)D); break;
+    case DR_I32: go(ild_dense_int<R, int32_t>, 4, (const int32_t*)D); break;
+    case DR_I64: go(ild_dense_int<R, int64_t>, 4, (const int64_t*)D); break;
     default:
       dr::set_error("dr_ild_dense: dist dtype must be DR_F32, DR_F64, DR_I32 or DR_I64");
       return DR_EUNSUPPORTED;
@@ -951,42 +909,51 @@ int launch_dense(const R* recs, int64_t n_users, int k, const void* D, int dd, i
   return DR_OK;
 }
 
+// dr_ild_dense (out) and dr_ild_dense_pair_sum (raw); fn names the caller in
+// the error strings, as DR_CHECK_ARG / DR_CHECK_LAUNCH would.
+int ild_dense(const char* fn, const void* recs, int rec_dtype, int64_t n_users, int k,
+              const void* dist, int dist_dtype, int64_t n_items, float* out, double* raw,
+              int32_t* err, dr_stream_t stream) {
+  const auto fail = [fn](int rc, const std::string& msg) {
+    dr::set_error(std::string(fn) + ": " + msg);
+    return rc;
+  };
+  if (k < 1) return fail(DR_EINVAL, "k must be >= 1");
+  if (rec_dtype != DR_I32 && rec_dtype != DR_I64)
+    return fail(DR_EINVAL, "rec_dtype must be DR_I32/DR_I64");
+  if (n_users == 0) return DR_OK;
+  if (!recs || !dist || !(out || raw)) return fail(DR_EINVAL, "null pointer");
+  const int rc = with_recs(recs, rec_dtype, [&](auto* r) {
+    return launch_dense(r, n_users, k, dist, dist_dtype, n_items, out, raw, err, (hipStream_t)stream);
+  });
+  if (rc != DR_OK) return rc;
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(DR_EHIP, std::string("hipGetLastError() -> ") + hipGetErrorString(e));
+  return DR_OK;
+}
+
+template <typename R>
+void launch_labels(const R* recs, int64_t n_users, int k, const int64_t* labels, int64_t n_items,
+                   float* out, int32_t* err, hipStream_t s) {
+  const auto kernel = k <= kLabelMaxK ? ild_labels_kernel<R, true> : ild_labels_kernel<R, false>;
+  hipLaunchKernelGGL(kernel, (int)dr::ceil_div(n_users, 4), 256, 0, s, recs, n_users, k, labels,
+                     n_items, out, err);
+}
+
 }  // namespace
 
 extern "C" int dr_ild_dense(const void* recs, int rec_dtype, int64_t n_users, int k,
                             const void* dist, int dist_dtype, int64_t n_items, float* out,
                             int32_t* err, dr_stream_t stream) {
-  DR_CHECK_ARG(k >= 1, "k must be >= 1");
-  DR_CHECK_ARG(rec_dtype == DR_I32 || rec_dtype == DR_I64, "rec_dtype must be DR_I32/DR_I64");
-  if (n_users == 0) return DR_OK;
-  DR_CHECK_ARG(recs && dist && out, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = rec_dtype == DR_I32
-               ? launch_dense((const int32_t*)recs, n_users, k, dist, dist_dtype, n_items, out,
-                              nullptr, err, s)
-               : launch_dense((const int64_t*)recs, n_users, k, dist, dist_dtype, n_items, out,
-                              nullptr, err, s);
-  if (rc != DR_OK) return rc;
-  DR_CHECK_LAUNCH();
-  return DR_OK;
+  return ild_dense(__func__, recs, rec_dtype, n_users, k, dist, dist_dtype, n_items, out, nullptr,
+                   err, stream);
 }
 
 extern "C" int dr_ild_dense_pair_sum(const void* recs, int rec_dtype, int64_t n_users, int k,
                                      const void* dist, int dist_dtype, int64_t n_items,
                                      double* out, int32_t* err, dr_stream_t stream) {
-  DR_CHECK_ARG(k >= 1, "k must be >= 1");
-  DR_CHECK_ARG(rec_dtype == DR_I32 || rec_dtype == DR_I64, "rec_dtype must be DR_I32/DR_I64");
-  if (n_users == 0) return DR_OK;
-  DR_CHECK_ARG(recs && dist && out, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = rec_dtype == DR_I32
-               ? launch_dense((const int32_t*)recs, n_users, k, dist, dist_dtype, n_items, nullptr,
-                              out, err, s)
-               : launch_dense((const int64_t*)recs, n_users, k, dist, dist_dtype, n_items, nullptr,
-                              out, err, s);
-  if (rc != DR_OK) return rc;
-  DR_CHECK_LAUNCH();
-  return DR_OK;
+  return ild_dense(__func__, recs, rec_dtype, n_users, k, dist, dist_dtype, n_items, nullptr, out,
+                   err, stream);
 }
 
 extern "C" int dr_ild_labels(const void* recs, int rec_dtype, int64_t n_users, int k,
@@ -996,19 +963,9 @@ extern "C" int dr_ild_labels(const void* recs, int rec_dtype, int64_t n_users, i
   DR_CHECK_ARG(rec_dtype == DR_I32 || rec_dtype == DR_I64, "rec_dtype must be DR_I32/DR_I64");
   if (n_users == 0) return DR_OK;
   DR_CHECK_ARG(recs && labels && out, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const int grid = (int)dr::ceil_div(n_users, 4);
-#define DR_LAB(KERN, RT)                                                                   \
-  hipLaunchKernelGGL((KERN<RT>), grid, 256, 0, s, (const RT*)recs, n_users, k, labels, \
-                     n_items, out, err)
-  if (k <= kLabelMaxK) {  // the list's labels staged in LDS
-    if (rec_dtype == DR_I32) DR_LAB(ild_labels_kernel, int32_t);
-    else DR_LAB(ild_labels_kernel, int64_t);
-  } else {
-    if (rec_dtype == DR_I32) DR_LAB(ild_labels_long_kernel, int32_t);
-    else DR_LAB(ild_labels_long_kernel, int64_t);
-  }
-#undef DR_LAB
+  with_recs(recs, rec_dtype, [&](auto* r) {
+    launch_labels(r, n_users, k, labels, n_items, out, err, (hipStream_t)stream);
+  });
   DR_CHECK_LAUNCH();
   return DR_OK;
 }
@@ -1022,12 +979,10 @@ extern "C" int dr_ild_embedding(const void* recs, int rec_dtype, int64_t n_users
                "unknown distance kind");
   if (n_users == 0) return DR_OK;
   DR_CHECK_ARG(recs && item_table && out, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = rec_dtype == DR_I32
-               ? launch_embedding((const int32_t*)recs, n_users, k, (const __bf16*)item_table,
-                                  n_items, d, kind, out, err, s)
-               : launch_embedding((const int64_t*)recs, n_users, k, (const __bf16*)item_table,
-                                  n_items, d, kind, out, err, s);
+  const int rc = with_recs(recs, rec_dtype, [&](auto* r) {
+    return launch_embedding(r, n_users, k, (const __bf16*)item_table, n_items, d, kind, out, err,
+                            (hipStream_t)stream);
+  });
   if (rc != DR_OK) return rc;
   DR_CHECK_LAUNCH();
   return DR_OK;

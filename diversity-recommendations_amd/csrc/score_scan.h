@@ -46,6 +46,7 @@ namespace dr_topk {
 
 using dr::bf16x8;
 using dr::f32x16;
+using dr::wave_lds_sync;
 
 // Diagnostic build (-DDR_TOPK_DIAG, libdivrec_hip_diag.so only): per-wave
 // s_memtime cycle counters of each phase of the scan, written to the tail of
@@ -158,7 +159,7 @@ constexpr bool mfma16_scan(int w, int cap, bool f32, bool gmax) {
 
 // D = W, the row's width in bf16 units (row bytes / 2); HALF: half_issue()
 template <int D, int CAP, bool HALF = false>
-struct TileGeom {
+struct TileGeom : dr::RowSwizzle<D> {  // CPR, swz(row): the stage's XOR swizzle
   static constexpr int WAVES = kWavesScan;
   static constexpr int THREADS = WAVES * 64;
   static constexpr int ISSUERS = HALF ? 4 : WAVES;       // waves that issue the ring refill
@@ -167,18 +168,12 @@ struct TileGeom {
   // LDS-DMA instructions per issuing wave per stage (one moves 64 * 16 B)
   static constexpr int LPT = STAGE_BYTES / 16 / (ISSUERS * 64);
   static constexpr int KSTEPS = D / 16;                 // MFMA k-steps per row
-  static constexpr int CPR = D / 8;                     // 16-B chunks per row
   static constexpr int TILE_BYTES = kTileItems * D * 2;
   static constexpr int SR = STAGE_BYTES / TILE_BYTES;   // row tiles per stage
   static_assert(LPT >= 1 && STAGE_BYTES % (16 * ISSUERS * 64) == 0, "stage geometry");
   static_assert(RING >= 2, "ring depth");
-  static constexpr int RPB = (2 * D >= 256) ? 1 : 256 / (2 * D);  // rows per 256-B bank row
-  static constexpr int SWM = (CPR < 16 ? CPR : 16) - 1;
   static constexpr int MARGIN = SR * kTileItems;  // max new keys per user per stage
   static_assert(SR >= 1, "a stage holds at least one tile");
-  // physical chunk = logical chunk ^ swz(row): spreads the 32 rows that one
-  // A-fragment ds_read_b128 touches over distinct 16-B bank slots.
-  __device__ static int swz(int r) { return (r / RPB) & SWM; }
 };
 
 // User tiles (of 32) per wave. The B fragments take NU_T*KSTEPS*4 VGPRs (128 at
@@ -343,12 +338,6 @@ __device__ __forceinline__ bool sorted_contains(const int32_t* __restrict__ list
   return lo < n && list[lo] == item;
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ int lane_prefix(uint64_t bal) {  // set bits of bal below this lane
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
                                         __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
@@ -388,7 +377,7 @@ __device__ __forceinline__ float hot_max16(const f32x16& a) {
 __device__ __forceinline__ bool hot(float m, float thr) { return !(m <= thr); }
 
 // Item row (within its tile) of score register r of a lane of half-wave h.
-__host__ __device__ constexpr int score_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+__host__ __device__ constexpr int score_row(int r, int h) { return dr::tile_row(r, h); }
 // The partial-tile rule: bit r is set iff score register r is a row of the
 // slice, `left` rows of which remain from the tile's first (all 16 but in the
 // slice's last tile, whose rows past the end repeat the last row).

@@ -871,6 +871,91 @@ def test_ild_embedding_stream_small_grids():
         assert np.allclose(got[:50], ref, rtol=2e-5, atol=1e-6)
 
 
+_ILD_BAD_LIST_ROUTES = (
+    [("dense", dt, 5) for dt in (torch.float32, torch.float64, torch.int32, torch.int64)]
+    + [("pair_sum", dt, 5) for dt in (torch.float32, torch.int64)]
+    + [("labels", None, 5), ("labels", None, 1025)]  # staged in LDS / read through the cache
+    # (d, kind, ild_stream), k: per user (d = 64), streamed and per user both ways at d = 128,
+    # the d = 256 kernel, long lists
+    + [("embedding", (64, "cosine", None), 10), ("embedding", (128, "cosine", None), 64),
+       ("embedding", (128, "cosine", 0), 64), ("embedding", (128, "euclidean", None), 64),
+       ("embedding", (128, "euclidean", 1), 64), ("embedding", (256, "dot", None), 10),
+       ("embedding", (32, "cosine", None), 129)])
+
+
+@pytest.mark.parametrize("route,arg,k", _ILD_BAD_LIST_ROUTES,
+                         ids=lambda v: str(v).replace("torch.", "").replace(" ", ""))
+@pytest.mark.parametrize("rec_dtype", [torch.int32, torch.int64])
+def test_ild_bad_lists_give_nan_and_count_once(route, arg, k, rec_dtype):
+    """The bad-list contract (include/divrec_hip.h) of every ILD kernel, through
+    the C ABI: a list with an id outside [0, n_items) gives NaN for its user
+    and adds one to *err however many of its ids are bad; every other user's
+    value is the one the clean lists give, bit for bit; a null err is allowed.
+    9 users are three 4-wave workgroups, the last with one wave (nine one-wave
+    workgroups for long embedding lists); the one-lane-per-user dense kernels
+    get 260 users, two workgroups. Bad users: the first, one in the middle
+    and the last."""
+    L, dev = _backend.lib(), torch.device(DEV)
+    one_lane = route in ("dense", "pair_sum") and arg.is_floating_point
+    nu = 260 if one_lane else 9
+    n_items = 50 if route in ("dense", "pair_sum") else 300
+    rng = np.random.default_rng(k)
+    clean = rng.integers(0, n_items, size=(nu, k))
+    bad_users = [0, 4, nu - 1]
+    bad = clean.copy()
+    bad[0, 0] = -1
+    bad[4, k - 1] = n_items
+    bad[nu - 1, 0], bad[nu - 1, k - 1] = -1, n_items  # two bad ids: counted once
+    rdt = _backend.dtype_code(rec_dtype)
+    knobs = {}
+    if route in ("dense", "pair_sum"):
+        D = torch.from_numpy(rng.integers(0, 3, size=(n_items, n_items))).to(DEV, arg)
+        fn = L.dr_ild_dense if route == "dense" else L.dr_ild_dense_pair_sum
+        out_dtype = torch.float32 if route == "dense" else torch.float64
+
+        def call(rt, out, err):
+            return fn(rt.data_ptr(), rdt, nu, k, D.data_ptr(), _backend.dtype_code(arg), n_items,
+                      out.data_ptr(), _backend.ptr(err), _backend.stream(dev))
+    elif route == "labels":
+        labels = torch.from_numpy(rng.integers(0, 4, size=n_items)).to(DEV)
+        out_dtype = torch.float32
+
+        def call(rt, out, err):
+            return L.dr_ild_labels(rt.data_ptr(), rdt, nu, k, labels.data_ptr(), n_items,
+                                   out.data_ptr(), _backend.ptr(err), _backend.stream(dev))
+    else:
+        d, kind, forced = arg
+        E = _bf16(oracle.as_bf16_f32(rng.standard_normal((n_items, d)).astype(np.float32)))
+        out_dtype = torch.float32
+        if forced is not None:
+            knobs = {"ild_stream": forced}
+
+        def call(rt, out, err):
+            return L.dr_ild_embedding(rt.data_ptr(), rdt, nu, k, E.data_ptr(), n_items, d,
+                                      {"cosine": 0, "dot": 1, "euclidean": 2}[kind],
+                                      out.data_ptr(), _backend.ptr(err), _backend.stream(dev))
+
+    def run(lists, with_err):
+        rt = torch.from_numpy(lists).to(DEV, rec_dtype)
+        out = torch.zeros(nu, dtype=out_dtype, device=DEV)
+        err = _backend.error_counter(dev) if with_err else None
+        with _backend.plan_knobs(**knobs):
+            assert call(rt, out, err) == 0, L.dr_last_error()
+        return out.cpu().numpy(), (int(err.item()) if with_err else None)
+
+    want, n0 = run(clean, True)
+    assert n0 == 0 and not np.isnan(want).any()
+    is_bad = np.zeros(nu, bool)
+    is_bad[bad_users] = True
+    for with_err in ((True, False) if route == "embedding" else (True,)):
+        got, n = run(bad, with_err)
+        assert got.dtype == (np.float64 if route == "pair_sum" else np.float32)
+        if with_err:
+            assert n == 3
+        assert np.array_equal(np.isnan(got), is_bad)
+        assert np.array_equal(got[~is_bad], want[~is_bad])
+
+
 # --------------------------------------------------------------------------- BPR + Adam
 @pytest.mark.parametrize("d", [100, 128, 256])  # 100: the reference experiments' embedding_dim
 def test_bpr_fwd_bwd(d):

@@ -8,9 +8,13 @@ joined by "+" (e.g. "ild_stream=0": the one-wave-per-user kernel), optionally
 prefixed by a library tag "TAG@" (libdivrec_hip_TAG.so, a --variant build of
 build_native.py; default the product library). Variants run
 round-robin on the same device inputs, timed with HIP events on the current
-stream; every variant's output must equal the first one's bit for bit (the
-streamed and per-user kernels sum the same pairs in the same order). Prints
-one JSON line; exit status 1 on a mismatch.
+stream. Every variant's output is compared with the first one's bit for bit
+("identical" in the record; exit status 1 when any differs). Two builds or
+ring depths of one kernel must be identical; the streamed and the per-user
+kernel are not (the streamed one sums each Gram column weighted, so the fp32
+rounding differs: tests/test_hip_kernels.py holds them to rel 2e-5), so list
+only variants of one kernel when the exit status matters. Prints one JSON
+line.
 """
 import argparse
 import json
@@ -124,7 +128,7 @@ def main():
         med = statistics.median(times[t])
         same = bool(torch.equal(outs[t], outs[tags[0]]))
         bad |= not same
-        res["variants"][t] = {"median_ms": med, "min_ms": min(times[t]),
+        res["variants"][t] = {"median_ms": med, "min_ms": min(times[t]), "max_ms": max(times[t]),
                               "users_per_s": args.users / med * 1e3,
                               "gbs": per_user * args.users / med / 1e6,
                               "frac_of_8tbs": per_user * args.users / med / 1e6 / 8000,
