@@ -67,6 +67,8 @@ SIGNATURES = {
     "dr_ild_dense_pair_sum": (_i32, [_p, _i32, _i64, _i32, _p, _i32, _i64, _p, _p, _p]),
     "dr_ild_labels": (_i32, [_p, _i32, _i64, _i32, _p, _i64, _p, _p, _p]),
     "dr_ild_embedding": (_i32, [_p, _i32, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _p]),
+    "dr_ild_embedding_backward": (_i32, [_p, _i32, _i64, _i32, _p, _i64, _i32, _i32, _p, _f32, _p,
+                                         _p, _p]),
     "dr_bpr_fwd_bwd": (_i32, [_p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _f32, _p, _p, _p, _p,
                               _p, _p]),
     "dr_mse_fwd_bwd": (_i32, [_p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _f32, _p, _p, _p, _p,

@@ -7,7 +7,10 @@
     reference's Python sum (bit-identical values);
   * ``EmbeddingDistance(item_table, kind)`` — D computed on the fly from item
     embeddings ('cosine', 'dot', 'euclidean'; dr_ild_embedding, bf16 MFMA Gram
-    tiles) for catalogs where an I x I matrix cannot exist;
+    tiles) for catalogs where an I x I matrix cannot exist; with
+    ``differentiable=True`` over an fp32 parameter the value carries a
+    gradient for the table (dr_ild_embedding_backward), so it can be trained
+    against (train.diversity_pair_wise_train_loop);
   * ``LabelEquality(labels)`` — D[i,j] = (labels[i] == labels[j]) on the fly
     (dr_ild_labels), what IntraListBinaryUnfairnessScore builds densely.
 
@@ -41,11 +44,22 @@ class EmbeddingDistance:
 
     KINDS = ("cosine", "dot", "euclidean")
 
-    def __init__(self, item_table: torch.Tensor, kind: str = "cosine"):
+    def __init__(self, item_table: torch.Tensor, kind: str = "cosine",
+                 differentiable: bool = False):
         if kind not in self.KINDS:
             raise ValueError(f"kind must be one of {self.KINDS}")
+        if differentiable:
+            if item_table.dtype != torch.float32 or item_table.dim() != 2:
+                raise ValueError("a differentiable EmbeddingDistance needs a 2-D fp32 item_table")
+            if item_table.size(1) > ops.ILD_GRAD_MAX_D:
+                raise ValueError(f"a differentiable EmbeddingDistance supports embedding_dim <= "
+                                 f"{ops.ILD_GRAD_MAX_D}, got {item_table.size(1)}")
+            if not item_table.is_cuda:
+                raise ValueError("a differentiable EmbeddingDistance needs item_table on the "
+                                 "ROCm device")
         self.kind = kind
         self.item_table = item_table
+        self.differentiable = bool(differentiable)
         self._dev_table = None
         self._key = None
 
@@ -81,6 +95,27 @@ class LabelEquality:
         return self._dev
 
 
+class _EmbeddingILD(torch.autograd.Function):
+    """ILD per list as a function of the fp32 item table, for fixed lists.
+    Forward: the value ops.ild_embedding gives from the distance's bf16 copy.
+    Backward: dr_ild_embedding_backward on the fp32 table, a dense gradient
+    (the regulariser's gradient, not a bitwise adjoint of the bf16 value)."""
+
+    @staticmethod
+    def forward(ctx, item_table, recs, distance):
+        ctx.save_for_backward(item_table, recs)
+        ctx.kind = distance.kind
+        return ops.ild_embedding(recs, distance.table(recs.device), distance.kind)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        item_table, recs = ctx.saved_tensors
+        table = item_table.detach()
+        grad = torch.zeros(table.shape, dtype=table.dtype, device=table.device)
+        ops.ild_embedding_backward(recs, table, ctx.kind, grad, grad_out=grad_out)
+        return grad, None, None
+
+
 DistanceLike = Union[torch.Tensor, EmbeddingDistance, LabelEquality]
 
 
@@ -107,6 +142,11 @@ class IntraListDiversityScore(RecommendationsAwareLoss):
         recs = recommendations.to(dev)
         D = self.distance_matrix
         if isinstance(D, EmbeddingDistance):
+            if D.differentiable and D.item_table.requires_grad and torch.is_grad_enabled():
+                if recs.dim() == 2 and recs.size(1) > ops.ILD_GRAD_MAX_K:
+                    raise ValueError(f"the differentiable embedding ILD supports lists of at most "
+                                     f"{ops.ILD_GRAD_MAX_K} items, got {recs.size(1)}")
+                return _EmbeddingILD.apply(D.item_table, recs.to(D.item_table.device), D)
             return ops.ild_embedding(recs, D.table(dev), D.kind)
         if isinstance(D, LabelEquality):
             return ops.ild_labels(recs, D.device_labels(dev))

@@ -425,6 +425,57 @@ def ild_embedding(recs: torch.Tensor, item_table: torch.Tensor, kind: str = "cos
     return out
 
 
+ILD_GRAD_MAX_K, ILD_GRAD_MAX_D = 128, 256  # dr_ild_embedding_backward's bounds
+
+
+def ild_embedding_backward(
+    recs: torch.Tensor,
+    item_table: torch.Tensor,
+    kind: str,
+    grad_item: torch.Tensor,
+    grad_out: Optional[torch.Tensor] = None,
+    scale: float = 1.0,
+    err: Optional[torch.Tensor] = None,
+    check: bool = True,
+) -> None:
+    """Adds to ``grad_item`` the gradient of ``scale * sum_u grad_out[u] * ILD_u``
+    with respect to the fp32 ``item_table`` (dr_ild_embedding_backward; the
+    closed forms are in include/divrec_hip.h). ``grad_out`` None means all
+    ones. Lists of 1 <= k <= 128 ids, any width d <= 256. Ids are range-checked
+    on the device (a list with an invalid id adds nothing): with ``check`` and
+    no ``err`` the call reads the count (one sync) and raises IndexError;
+    otherwise the count goes to the caller's ``err`` (may be None), checked by
+    the caller."""
+    dev = B.require_device(recs, item_table, grad_item, grad_out)
+    recs, rc_dt = _recs(recs)
+    _need(item_table.dtype == torch.float32 and item_table.dim() == 2, "item_table must be fp32 2-D")
+    _contig(item_table, "item_table")
+    _need(grad_item.shape == item_table.shape and grad_item.dtype == torch.float32
+          and grad_item.is_contiguous(),
+          "grad_item must be a contiguous fp32 tensor shaped like item_table")
+    _need(kind in _KINDS, f"kind must be one of {sorted(_KINDS)}")
+    n, k = recs.shape
+    _need(1 <= k <= ILD_GRAD_MAX_K, f"embedding ILD gradient supports 1 <= k <= {ILD_GRAD_MAX_K}")
+    _need(1 <= item_table.size(1) <= ILD_GRAD_MAX_D,
+          f"embedding ILD gradient supports embedding_dim <= {ILD_GRAD_MAX_D}")
+    if grad_out is not None:
+        _need(grad_out.dim() == 1 and grad_out.numel() == n, "grad_out must be 1-D, one per list")
+        grad_out = grad_out.to(torch.float32).contiguous()
+    if n == 0:
+        return
+    own = err is None and check
+    if own:
+        err = B.error_counter(dev)
+    rc = B.lib().dr_ild_embedding_backward(
+        recs.data_ptr(), rc_dt, n, k, item_table.data_ptr(), item_table.size(0),
+        item_table.size(1), _KINDS[kind], B.ptr(grad_out), float(scale), grad_item.data_ptr(),
+        B.ptr(err), B.stream(dev),
+    )
+    B.check(rc, "dr_ild_embedding_backward")
+    if own:
+        B.raise_if_out_of_range(err, "dr_ild_embedding_backward")
+
+
 # --------------------------------------------------------------------------- BPR
 def bpr_fwd_bwd(
     user_table: torch.Tensor,

@@ -1,4 +1,5 @@
 from .utils import (
+    diversity_pair_wise_train_loop,
     fused_adam_step,
     get_model_recommendations,
     pair_wise_score_loop,
@@ -16,6 +17,7 @@ __all__ = [
     "recommendations_score_loop",
     "point_wise_train_loop",
     "pair_wise_train_loop",
+    "diversity_pair_wise_train_loop",
     "recommendations_train_loop",
     "fused_adam_step",
 ]

@@ -17,6 +17,9 @@ Same functions, arguments and return values as the reference. On the hot path:
 * ``point_wise_train_loop`` with MatrixFactorization + MSELoss on fp32 targets
   runs each batch as ONE dr_mse_fwd_bwd followed by the same optimizer steps,
   and ``point_wise_score_loop`` with MSELoss losses as its forward-only form.
+* ``diversity_pair_wise_train_loop`` (not in the reference) trains the BPR
+  objective minus a weighted ILD of the model's own top-k lists: the pairwise
+  part as above, the regulariser's gradient by dr_ild_embedding_backward.
 """
 from __future__ import annotations
 
@@ -29,6 +32,8 @@ from torch.autograd.graph import increment_version
 from divrec import _backend, ops
 from divrec.datasets import PairWiseDataset, PointWiseDataset, RankingDataset
 from divrec.losses import (
+    EmbeddingDistance,
+    IntraListDiversityScore,
     LogSigmoidDifferenceLoss,
     MSELoss,
     PairWiseLoss,
@@ -354,6 +359,44 @@ def _bpr_fast_path(model, loss, scores) -> bool:
             and (scores is None or all(type(s) is AUCScore for s in scores)))
 
 
+def _bpr_fused_batch(model: MatrixFactorization, user_id, pos, neg, epoch_err):
+    """One batch of the fused BPR path: range checks, then ONE dr_bpr_fwd_bwd
+    that adds the batch's dense gradients into the embeddings' ``.grad`` (the
+    'mean' reduction). No optimizer step. Returns (uid, pid, nid, per-triple
+    losses, hit flags, epoch_err), the ids on the model's device; epoch_err is
+    the epoch's id range counter (made here on the first batch)."""
+    dev = model._device()
+    U, I = model.user_embeddings.weight, model.item_embeddings.weight
+    host = user_id.device.type == "cpu"
+    if host:  # host batches: raise before any compute
+        _backend.host_ids_in_range(user_id, U.size(0), "user_id")
+        _backend.host_ids_in_range(pos, I.size(0), "positive item_id")
+        _backend.host_ids_in_range(neg, I.size(0), "negative item_id")
+    uid, pid, nid = (t.to(dev, torch.int64, non_blocking=True) for t in (user_id, pos, neg))
+    if not host and uid.numel():
+        # device batches: one min/max reduction read back (one sync)
+        # BEFORE the kernel, so a bad batch raises IndexError with the
+        # weights, the optimizer state and the gradient tables as they
+        # were (the reference's nn.Embedding fails before any backward;
+        # the lazy path's all-zero gradient invariant holds)
+        mm = torch.stack([uid.min(), uid.max(), torch.minimum(pid.min(), nid.min()),
+                          torch.maximum(pid.max(), nid.max())]).cpu().tolist()
+        if mm[0] < 0 or mm[1] >= U.size(0):
+            raise IndexError("index out of range in self (user_id)")
+        if mm[2] < 0 or mm[3] >= I.size(0):
+            raise IndexError("index out of range in self (item_id)")
+    if U.grad is None:
+        U.grad = torch.zeros_like(U)
+    if I.grad is None:
+        I.grad = torch.zeros_like(I)
+    if epoch_err is None:
+        epoch_err = _backend.error_counter(dev)
+    B = uid.numel()
+    losses_b, hits = ops.bpr_fwd_bwd(U.data, I.data, uid, pid, nid, 1.0 / B, U.grad, I.grad,
+                                     err=epoch_err, check=False)
+    return uid, pid, nid, losses_b, hits, epoch_err
+
+
 def pair_wise_train_loop(dataset: PairWiseDataset, model: RankingModel, loss: PairWiseLoss,
                          optimizer: torch.optim.Optimizer,
                          scores: Optional[List[PairWiseLoss]] = None,
@@ -369,35 +412,10 @@ def pair_wise_train_loop(dataset: PairWiseDataset, model: RankingModel, loss: Pa
     epoch_err = None  # id range errors of the fused kernel on device batches
     for user_id, pos, neg, uf, pf, nf in dataset.loader(**loader_params):
         if fused:
-            dev = model._device()
             U, I = model.user_embeddings.weight, model.item_embeddings.weight
-            host = user_id.device.type == "cpu"
-            if host:  # host batches: raise before any compute
-                _backend.host_ids_in_range(user_id, U.size(0), "user_id")
-                _backend.host_ids_in_range(pos, I.size(0), "positive item_id")
-                _backend.host_ids_in_range(neg, I.size(0), "negative item_id")
-            uid, pid, nid = (t.to(dev, torch.int64, non_blocking=True) for t in (user_id, pos, neg))
-            if not host and uid.numel():
-                # device batches: one min/max reduction read back (one sync)
-                # BEFORE the kernel, so a bad batch raises IndexError with the
-                # weights, the optimizer state and the gradient tables as they
-                # were (the reference's nn.Embedding fails before any backward;
-                # the lazy path's all-zero gradient invariant holds)
-                mm = torch.stack([uid.min(), uid.max(), torch.minimum(pid.min(), nid.min()),
-                                  torch.maximum(pid.max(), nid.max())]).cpu().tolist()
-                if mm[0] < 0 or mm[1] >= U.size(0):
-                    raise IndexError("index out of range in self (user_id)")
-                if mm[2] < 0 or mm[3] >= I.size(0):
-                    raise IndexError("index out of range in self (item_id)")
-            if U.grad is None:
-                U.grad = torch.zeros_like(U)
-            if I.grad is None:
-                I.grad = torch.zeros_like(I)
-            if epoch_err is None:
-                epoch_err = _backend.error_counter(dev)
+            uid, pid, nid, losses_b, hits, epoch_err = _bpr_fused_batch(model, user_id, pos, neg,
+                                                                        epoch_err)
             B = uid.numel()
-            losses_b, hits = ops.bpr_fwd_bwd(U.data, I.data, uid, pid, nid, 1.0 / B, U.grad, I.grad,
-                                             err=epoch_err, check=False)
             loss_value = torch.sum(losses_b, dim=0) / B
             if lazy:  # touched rows only; the kernel zeroes those gradient rows
                 lazy_adam_step(optimizer, {U: torch.unique(uid),
@@ -424,6 +442,10 @@ def pair_wise_train_loop(dataset: PairWiseDataset, model: RankingModel, loss: Pa
                 batch_scores.append(torch.stack(
                     [s(positives.detach(), negatives.detach()).double() for s in scores]))
     _backend.raise_if_out_of_range(epoch_err, "pair_wise_train_loop")
+    return _pair_wise_epoch_means(batch_losses, batch_scores, n_scores)
+
+
+def _pair_wise_epoch_means(batch_losses, batch_scores, n_scores) -> Tuple[float, List[float]]:
     count = len(batch_losses)
     # per-batch values summed as Python floats in batch order, like the reference
     mean_loss = sum(float(v) for v in torch.stack(batch_losses).double().cpu().tolist()) / count
@@ -432,6 +454,102 @@ def pair_wise_train_loop(dataset: PairWiseDataset, model: RankingModel, loss: Pa
         rows = torch.stack(batch_scores).double().cpu().tolist()
         means = [sum(r[i] for r in rows) / count for i in range(n_scores)]
     return mean_loss, means
+
+
+def diversity_pair_wise_train_loop(dataset: PairWiseDataset, model: MatrixFactorization,
+                                   loss: PairWiseLoss, optimizer: torch.optim.Optimizer,
+                                   diversity: IntraListDiversityScore, diversity_weight: float,
+                                   number_of_recommendations: int,
+                                   scores: Optional[List[PairWiseLoss]] = None,
+                                   **loader_params) -> Tuple[float, List[float], float]:
+    """One epoch of pairwise training with a diversity regulariser; returns
+    (mean batch loss, [mean score], mean ILD of the batches' lists).
+
+    Per batch the objective is
+        loss(pos, neg) - diversity_weight * mean_{u in unique(batch users)} ILD_u(L_u)
+    where L_u = model.score_topk(number_of_recommendations, user_ids=those
+    users) under the current parameters. The lists are CONSTANTS of the step:
+    no gradient flows through the selection, only through the embeddings of
+    the items a list holds (dr_ild_embedding_backward on the fp32 item table).
+
+    The pairwise part runs exactly as in pair_wise_train_loop (the fused
+    dr_bpr_fwd_bwd for MatrixFactorization + LogSigmoidDifferenceLoss,
+    autograd otherwise) and leaves its gradients in ``.grad``; the regulariser
+    adds into ``item_embeddings.weight.grad``; then the optimizer steps as
+    there (dr_adam_dense for a plain Adam, dr_adam_rows for SparseAdam over
+    the batch's rows and the lists' items, ``optimizer.step()`` otherwise).
+    ``model`` must be a MatrixFactorization and ``diversity`` an
+    IntraListDiversityScore over EmbeddingDistance(model.item_embeddings.weight,
+    kind, differentiable=True); anything else raises ValueError before any
+    compute. The returned loss and scores are those of pair_wise_train_loop
+    (the regulariser is not part of them)."""
+    assert scores is None or all(score.reduce for score in scores)
+    D = getattr(diversity, "distance_matrix", None)
+    if not isinstance(model, MatrixFactorization):
+        raise ValueError("diversity_pair_wise_train_loop needs a MatrixFactorization model")
+    if not (isinstance(diversity, IntraListDiversityScore) and isinstance(D, EmbeddingDistance)
+            and D.differentiable):
+        raise ValueError("diversity must be an IntraListDiversityScore over "
+                         "EmbeddingDistance(..., differentiable=True)")
+    if D.item_table is not model.item_embeddings.weight:
+        raise ValueError("diversity's EmbeddingDistance must be over model.item_embeddings.weight")
+    k = int(number_of_recommendations)
+    if not 2 <= k <= min(ops.ILD_GRAD_MAX_K, model.no_items):
+        raise ValueError(f"number_of_recommendations must be in [2, "
+                         f"{min(ops.ILD_GRAD_MAX_K, model.no_items)}], got {k}")
+    model.train()
+    n_scores = len(scores) if scores is not None else 0
+    batch_losses, batch_scores, batch_ilds = [], [], []
+    fused = _bpr_fast_path(model, loss, scores)
+    adam = fused and _plain_adam(optimizer)  # the generic path steps the optimizer itself
+    lazy = fused and _plain_sparse_adam(optimizer)
+    dev = model._device()
+    epoch_err = None  # id range errors of the kernels on device batches
+    for user_id, pos, neg, uf, pf, nf in dataset.loader(**loader_params):
+        U, I = model.user_embeddings.weight, model.item_embeddings.weight
+        if fused:
+            uid, pid, nid, losses_b, hits, epoch_err = _bpr_fused_batch(model, user_id, pos, neg,
+                                                                        epoch_err)
+            loss_value = torch.sum(losses_b, dim=0) / uid.numel()
+            if n_scores:
+                batch_scores.append(torch.stack(
+                    [s.reduce_loss_values(hits).double() for s in scores]))
+        else:
+            positives = model(user_id, pos, uf, pf)
+            negatives = model(user_id, neg, uf, nf)
+            loss_value = loss(positives, negatives)
+            loss_value.backward()
+            uid = user_id.to(dev, torch.int64)
+            if n_scores:
+                batch_scores.append(torch.stack(
+                    [s(positives.detach(), negatives.detach()).double() for s in scores]))
+        batch_losses.append(loss_value.detach())
+        # the regulariser: the lists of the batch's users under the current
+        # parameters, their ILD, and its gradient added to the item table's
+        users = torch.unique(uid)
+        with torch.no_grad():
+            items, _ = model.score_topk(k, user_ids=users)
+            batch_ilds.append(diversity.per_user(items).mean())
+        if I.grad is None:
+            I.grad = torch.zeros_like(I)
+        if epoch_err is None:
+            epoch_err = _backend.error_counter(dev)
+        ops.ild_embedding_backward(items, I.data, D.kind, I.grad,
+                                   scale=-float(diversity_weight) / users.numel(),
+                                   err=epoch_err, check=False)
+        if lazy:  # the lists' items are touched rows too: their gradient rows are zeroed
+            lazy_adam_step(optimizer, {U: users,
+                                       I: torch.unique(torch.cat([pid, nid, items.reshape(-1)]))})
+        elif adam:
+            fused_adam_step(optimizer)
+            optimizer.zero_grad()
+        else:
+            optimizer.step()
+            optimizer.zero_grad()
+    _backend.raise_if_out_of_range(epoch_err, "diversity_pair_wise_train_loop")
+    mean_loss, means = _pair_wise_epoch_means(batch_losses, batch_scores, n_scores)
+    ilds = torch.stack(batch_ilds).double().cpu().tolist()
+    return mean_loss, means, sum(ilds) / len(ilds)
 
 
 def recommendations_train_loop(dataset: RankingDataset, model: RankingModel,

@@ -257,6 +257,31 @@ int dr_ild_embedding(const void* recs, int rec_dtype, int64_t n_users, int k,
                      const void* item_table, int64_t n_items, int d, int kind, float* out,
                      int32_t* err, dr_stream_t stream);
 
+/* Gradient of the embedding ILD with respect to the item table: for every
+ * list u and position p, ADDS to grad_item[r[u,p], :] the derivative of
+ * scale * grad_out[u] * ILD_u, ILD_u = (sum_{p<q} D(e_p, e_q)) / (k (k - 1)),
+ * with respect to row r[u,p]. With w = scale * grad_out[u] / (k (k - 1)),
+ * e_p = item_table[r[u,p]] and sums over POSITIONS (a repeated item is two
+ * positions of one row, as in the forward):
+ *   dot:        row p += w (S - e_p),  S = sum_q e_q
+ *   cosine:     n_p = |e_p|, u_p = e_p / n_p, t_p = (sum_q u_q) - u_p;
+ *               row p += -w (t_p - (u_p . t_p) u_p) / n_p
+ *               (a position whose row has zero norm gets no gradient and does
+ *               not enter the sum; no NaN or Inf reaches grad_item)
+ *   euclidean:  row p += w sum_{q != p, |e_p - e_q| > 0} (e_p - e_q) / |e_p - e_q|
+ *               (pairs at distance exactly 0, a repeated item among them, add
+ *               nothing; the distance is formed from the differences)
+ * item_table is the fp32 [n_items, d] master table (not the forward's bf16
+ * copy), 1 <= d <= 256 (any d); grad_item fp32 of the same shape, owned and
+ * zeroed by the caller, accumulated with atomics; grad_out fp32 [n_users], NULL
+ * = all ones. 1 <= k <= 128 (k = 1 adds nothing); n_users = 0 is a no-op. A
+ * list holding an id outside [0, n_items) adds nothing for any of its
+ * positions and counts once in *err (id range checks, above). */
+int dr_ild_embedding_backward(const void* recs, int rec_dtype, int64_t n_users, int k,
+                              const float* item_table, int64_t n_items, int d, int kind,
+                              const float* grad_out, float scale, float* grad_item,
+                              int32_t* err, dr_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * BPR step (pair_wise_train_loop, divrec/train/utils.py:144-152, with
  * LogSigmoidDifferenceLoss, divrec/losses/log_sigmoid_difference_loss.py:11-14):
