@@ -20,6 +20,10 @@ Any ``embedding_dim`` works: widths without a scan instance (e.g. the
 reference experiments' 100) are zero-padded per call (a copy of O((U + I) d)
 bytes, small beside the O(U I d) scan; no cache, so writes through ``.data``
 or raw pointers, which bump no autograd version, are always seen).
+
+``recommend_diverse`` composes ``score_topk`` with a diversity re-rank of the
+top candidates (greedy DPP, dr_dpp_rerank, or MMR, dr_mmr_rerank) over the
+bf16 item table.
 """
 from __future__ import annotations
 
@@ -32,6 +36,8 @@ from divrec import ops
 from .base_models import RankingModel
 
 PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16}
+RERANKERS = ("dpp", "mmr")    # recommend_diverse methods
+MAX_RERANK_CANDIDATES = 1024  # C of dr_dpp_rerank / dr_mmr_rerank
 
 
 class _GatherDot(torch.autograd.Function):
@@ -146,3 +152,46 @@ class MatrixFactorization(RankingModel):
             ex = (exclude[0].to(dev, torch.int64), exclude[1].to(dev, torch.int32))
         scores, items = ops.score_topk(U, I, int(k), user_ids=uids, exclude=ex)
         return items.to(torch.int64), scores
+
+    @torch.no_grad()
+    def recommend_diverse(
+        self,
+        k: int,
+        candidates: int,
+        method: str = "dpp",
+        lam: float = 0.5,
+        user_ids: Optional[torch.Tensor] = None,
+        exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+        precision: str = "fp32",
+        n_items: Optional[int] = None,
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Diversity re-ranked lists: the top-``candidates`` items of each user
+        (``score_topk`` with the same ``user_ids`` / ``exclude`` / ``precision``
+        / ``n_items``) re-ranked to ``k`` picks by ``method`` "dpp"
+        (``ops.dpp_rerank``) or "mmr" (``ops.mmr_rerank``) at trade-off ``lam``
+        over the bf16 item table. Returns (items int64 [n, k] in pick order,
+        scores fp32 [n, k]: the picks' scan scores). A list that ends early
+        (fewer eligible candidates than ``k``) holds item -1 / score -inf.
+        ``k <= candidates <= min(1024, catalog)``, else ValueError."""
+        k, candidates = int(k), int(candidates)
+        if method not in RERANKERS:
+            raise ValueError(f"method must be one of {sorted(RERANKERS)}, got {method!r}")
+        catalog = self.no_items if n_items is None else int(n_items)
+        if not 1 <= k <= candidates <= min(MAX_RERANK_CANDIDATES, catalog):
+            raise ValueError(f"need 1 <= k <= candidates <= min({MAX_RERANK_CANDIDATES}, catalog "
+                             f"= {catalog}), got k = {k}, candidates = {candidates}")
+        cand, cand_scores = self.score_topk(candidates, user_ids=user_ids, exclude=exclude,
+                                            precision=precision, n_items=n_items)
+        table = self.bf16_tables()[1][:catalog]
+        cand32 = cand.to(torch.int32)
+        if method == "dpp":
+            picks, _ = ops.dpp_rerank(cand32, cand_scores, table, k, lam)
+        else:
+            picks = ops.mmr_rerank(cand32, cand_scores, table, k, lam)
+        picks = picks.to(torch.int64)
+        # the picks' scan scores: candidate ids are distinct per user, so a pick
+        # is found by a search in the user's sorted ids
+        ids_sorted, order = cand.sort(dim=1)
+        at = torch.searchsorted(ids_sorted, picks.contiguous()).clamp_(max=candidates - 1)
+        scores = cand_scores.gather(1, order.gather(1, at))
+        return picks, scores.masked_fill_(picks < 0, float("-inf"))

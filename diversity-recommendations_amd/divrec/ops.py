@@ -386,6 +386,7 @@ def ild_labels(recs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 _KINDS = {"cosine": B.DR_ILD_COSINE, "dot": B.DR_ILD_DOT, "euclidean": B.DR_ILD_EUCLIDEAN}
 ILD_WIDTHS = (32, 64, 128, 256)  # dr_ild_embedding instances; others are zero-padded
 MMR_WIDTHS = (64, 128)           # dr_mmr_rerank instances; others are zero-padded
+DPP_WIDTHS = (64, 128)           # dr_dpp_rerank instances; others are zero-padded
 
 
 def _width_of(widths, d: int, what: str) -> int:
@@ -696,6 +697,45 @@ def mmr_rerank(
     B.check(rc, "dr_mmr_rerank")
     B.raise_if_out_of_range(err, "dr_mmr_rerank")
     return out
+
+
+# --------------------------------------------------------------------------- DPP
+def dpp_rerank(
+    cand_items: torch.Tensor, cand_scores: torch.Tensor, item_table: torch.Tensor, k_out: int,
+    lam: float = 0.5, check: bool = True,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Greedy DPP MAP over per-user candidates (int32 [n, C] + fp32 [n, C]) ->
+    (items int32 [n, k_out], resid fp32 [n, k_out]): each pick maximises
+    lam * score + (1 - lam) * log(residual), the residual being the pick's
+    det-ratio against the picked set under the cosine Gram (include/divrec_hip.h).
+    ``resid`` holds each pick's residual when it was picked, so
+    ``resid.log().sum(1)`` is the list's log-determinant. A list that runs out
+    of eligible candidates (rank exhausted, duplicates only) ends in -1 / 0.
+    Candidate ids < 0 are empty slots; with ``check`` an id >= the table's row
+    count raises IndexError after the call (one counter read); without it such
+    candidates are silently never picked. Widths other than 64 / 128 are
+    zero-padded per call, as for ``mmr_rerank``."""
+    dev = B.require_device(cand_items, cand_scores, item_table)
+    _need(cand_items.dtype == torch.int32 and cand_scores.dtype == torch.float32,
+          "int32 candidate ids, fp32 scores")
+    _need(cand_items.dim() == 2 and cand_items.shape == cand_scores.shape, "[n, C] inputs")
+    _need(item_table.dtype == torch.bfloat16 and item_table.dim() == 2, "item_table must be bf16 2-D")
+    item_table = pad_columns(item_table.contiguous(),
+                             _width_of(DPP_WIDTHS, item_table.size(1), "dpp_rerank"))
+    n, C = cand_items.shape
+    out = torch.empty((n, int(k_out)), dtype=torch.int32, device=dev)
+    resid = torch.empty((n, int(k_out)), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out, resid
+    err = B.error_counter(dev) if check else None
+    rc = B.lib().dr_dpp_rerank(
+        cand_items.contiguous().data_ptr(), cand_scores.contiguous().data_ptr(), n, C,
+        item_table.data_ptr(), item_table.size(0), item_table.size(1), int(k_out),
+        float(lam), out.data_ptr(), resid.data_ptr(), B.ptr(err), B.stream(dev),
+    )
+    B.check(rc, "dr_dpp_rerank")
+    B.raise_if_out_of_range(err, "dr_dpp_rerank")
+    return out, resid
 
 
 # --------------------------------------------------------------------------- rank metrics

@@ -1,6 +1,7 @@
 from .utils import (
     diversity_pair_wise_train_loop,
     fused_adam_step,
+    get_diverse_recommendations,
     get_model_recommendations,
     pair_wise_score_loop,
     pair_wise_train_loop,
@@ -14,6 +15,7 @@ __all__ = [
     "point_wise_score_loop",
     "pair_wise_score_loop",
     "get_model_recommendations",
+    "get_diverse_recommendations",
     "recommendations_score_loop",
     "point_wise_train_loop",
     "pair_wise_train_loop",

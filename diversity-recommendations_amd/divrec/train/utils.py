@@ -43,6 +43,7 @@ from divrec.losses import (
 from divrec.metrics import AUCScore
 from divrec.metrics import _rank
 from divrec.models import MatrixFactorization, RankingModel
+from divrec.models.matrix_factorization import MAX_RERANK_CANDIDATES, RERANKERS
 
 
 def _model_device(model: torch.nn.Module) -> Optional[torch.device]:
@@ -179,6 +180,45 @@ def get_model_recommendations(dataset: RankingDataset, model: RankingModel,
             order = torch.sort(scores, descending=True, stable=True).indices
             recs.append(cands[order][:k].tolist())
     return torch.LongTensor(recs)
+
+
+def get_diverse_recommendations(dataset: RankingDataset, model: RankingModel,
+                                number_of_recommendations: int, candidates: int,
+                                method: str = "dpp", lam: float = 0.5) -> torch.LongTensor:
+    """Diversity re-ranked lists of every user of ``dataset`` (LongTensor
+    [U, k] on the CPU, not in the reference): the top-``candidates``
+    candidates of ``get_model_recommendations``' scan (fp32 scores, frozen
+    items excluded) re-ranked to ``number_of_recommendations`` picks by
+    ``MatrixFactorization.recommend_diverse`` (``method`` "dpp" or "mmr",
+    trade-off ``lam``). ValueError for a model outside the MF fast path, for
+    ragged candidate lists (as ``get_model_recommendations``) and for a list
+    that ends early (fewer eligible candidates than picks)."""
+    k, cands = int(number_of_recommendations), int(candidates)
+    if method not in RERANKERS:
+        raise ValueError(f"method must be one of {sorted(RERANKERS)}, got {method!r}")
+    if not 1 <= k <= cands <= MAX_RERANK_CANDIDATES:
+        raise ValueError(f"need 1 <= number_of_recommendations <= candidates <= "
+                         f"{MAX_RERANK_CANDIDATES}, got {k} and {cands}")
+    n_users = int(dataset.data.number_of_users)
+    n_items = int(dataset.data.number_of_items)
+    if not (_mf_scoring(model) and n_users <= model.no_users and n_items <= model.no_items):
+        raise ValueError("get_diverse_recommendations needs a MatrixFactorization model (its own "
+                         "forward) that covers the dataset's users and items")
+    if n_users == 0:
+        return torch.LongTensor([])
+    excl = dataset.exclusion_csr()
+    c_len = _list_length(dataset, excl, n_users, n_items, cands)
+    if c_len < k:
+        raise ValueError(f"a user has {c_len} candidates, fewer than the {k} recommendations asked for")
+    user_ids = None if n_users == model.no_users else torch.arange(n_users)
+    items, _ = model.recommend_diverse(k, c_len, method=method, lam=lam, user_ids=user_ids,
+                                       exclude=excl, n_items=n_items)
+    items = items.cpu()
+    if bool((items < 0).any()):
+        short = int((items < 0).any(dim=1).sum())
+        raise ValueError(f"{short} lists end before {k} picks (fewer eligible candidates: "
+                         f"duplicate or linearly dependent rows), so the lists are ragged")
+    return items
 
 
 def recommendations_score_loop(dataset: RankingDataset, model: RankingModel,

@@ -52,7 +52,7 @@ const char* dr_build_id(void);
 const char* dr_last_error(void);
 
 /* Planner knobs: process-wide overrides of dr_score_topk's launch planner (and
- * of dr_mmr_rerank's grid, DR_KNOB_SCAN_SLOTS), for tests and A/B timing runs
+ * of dr_mmr_rerank's and dr_dpp_rerank's grids, DR_KNOB_SCAN_SLOTS), for tests and A/B timing runs
  * only. Every plan gives identical results; only the time differs. The
  * library reads no environment variable: a knob holds the default plan until
  * it is set here, and value NaN restores the default. Thread-safe (atomic). */
@@ -401,6 +401,37 @@ int dr_catalog_histogram(const void* recs, int rec_dtype, int64_t n_users, int k
 int dr_mmr_rerank(const int32_t* cand_items, const float* cand_scores, int64_t n_users, int C,
                   const void* item_table, int64_t n_items, int d, int k_out, float lambda,
                   int32_t* out_items, int32_t* err, dr_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * DPP diversity re-rank (greedy MAP of a determinantal point process, Chen,
+ * Zhang, Zhou, NeurIPS 2018; no reference symbol, as for MMR): per user,
+ * greedily pick k_out of the C candidates maximising
+ *   lambda * score_i + (1 - lambda) * logf(r_i)
+ * over the live candidates with r_i > DR_DPP_EPS (ties -> lowest candidate
+ * position). x_i is the unit-normalised row of candidate i, S = <x_i, x_j> the
+ * cosine Gram matrix, and r_i = det S_{Y+i} / det S_Y = 1 - |P_Y x_i|^2 the
+ * residual of i given the picked set Y (the Schur complement of the
+ * incremental Cholesky of S). r_i starts at exactly 1.0f, so lambda = 0 makes
+ * the first pick a tie that position 0 wins. After pick j every candidate
+ * gets e_i = <b_t, x_i>, r_i -= e_i^2, b_t the t-th Gram-Schmidt vector of the
+ * picked rows (= (S_ji - sum_t' c_t'j c_t'i) / sqrt(r_j) of the Cholesky form).
+ * cand_items int32 [n_users, C], cand_scores fp32 [n_users, C], item_table
+ * bf16 [*, d]; out_items int32 [n_users, k_out] (item ids in selection order),
+ * out_resid fp32 [n_users, k_out] (may be NULL): r of each pick at the moment
+ * it was picked, so sum log(out_resid) is the list's log det S.
+ * 1 <= C <= 1024, 1 <= k_out <= min(C, 128), d in {64, 128}.
+ * Never eligible: r_i <= DR_DPP_EPS (duplicates of a pick, dependent rows: fp32
+ * leaves them at 0 +- 1e-6), candidate ids < 0 (empty slots), zero-norm rows;
+ * ids >= n_items are added to *err (int32 device counter, may be NULL) and
+ * never picked, their rows never read. When no eligible candidate is left
+ * (rank exhausted, k_out > d, all duplicates) the remaining picks are -1 with
+ * out_resid 0. n_items = 0 is DR_EINVAL.
+ * Launch: one workgroup per CU looping over the users (DR_KNOB_SCAN_SLOTS caps
+ * the grid, as for dr_mmr_rerank). */
+#define DR_DPP_EPS 1e-4f
+int dr_dpp_rerank(const int32_t* cand_items, const float* cand_scores, int64_t n_users, int C,
+                  const void* item_table, int64_t n_items, int d, int k_out, float lambda,
+                  int32_t* out_items, float* out_resid, int32_t* err, dr_stream_t stream);
 
 #ifdef __cplusplus
 }
