@@ -187,6 +187,72 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
   return v;
 }
 
+// ---------------------------------------------------------------- DPP reductions
+// Wave reductions on DPP lane moves (VALU, no LDS round trip), for the serial
+// chains of the re-rank kernels: quad swaps, half-row and row mirrors, then
+// row_bcast15 / 31 carry the running result into lane 63, which is read back
+// as a wave-uniform value.
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {  // v itself in masked-out rows
+  const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
+  const int nlo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xF, false);
+  const int nhi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xF, false);
+  return ((uint64_t)(uint32_t)nhi << 32) | (uint32_t)nlo;
+}
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+  v = umax64(v, dpp_u64<0xB1>(v));        // quad_perm [1,0,3,2]
+  v = umax64(v, dpp_u64<0x4E>(v));        // quad_perm [2,3,0,1]
+  v = umax64(v, dpp_u64<0x141>(v));       // row_half_mirror
+  v = umax64(v, dpp_u64<0x140>(v));       // row_mirror: every lane holds its row's max
+  v = umax64(v, dpp_u64<0x142, 0xA>(v));  // row_bcast15 into rows 1 and 3
+  v = umax64(v, dpp_u64<0x143, 0xC>(v));  // row_bcast31 into rows 2 and 3
+  return readlane_u64(v, 63);
+}
+__device__ __forceinline__ uint32_t wave_min_u32_64(uint32_t v) {
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x142, 0xA, 0xF, false));
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x143, 0xC, 0xF, false));
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+// Max over the wave's 64 lanes (lanes = 64) or over lanes 0..31 (lanes = 32)
+// by fused v_max_u32_dpp steps (one VALU each: the reduction is the latency
+// of the serial chains below); the result is read from the last lane.
+template <int LANES>
+__device__ __forceinline__ uint32_t wmax_u32(uint32_t v) {
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, true));
+  if constexpr (LANES == 64) {
+    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, true));
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+  } else {
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 31);
+  }
+}
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ float dpp_f32(float v) {  // 0 in masked-out rows
+  return __int_as_float(
+      __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
+}
+__device__ __forceinline__ float quad_sum_f32(float v) {  // every lane: its quad's sum
+  v += dpp_f32<0xB1>(v);
+  v += dpp_f32<0x4E>(v);
+  return v;
+}
+__device__ __forceinline__ float wave_sum_dpp_f32(float v) {  // uniform: the wave's sum
+  v = quad_sum_f32(v);
+  v += dpp_f32<0x141>(v);
+  v += dpp_f32<0x140>(v);
+  v += dpp_f32<0x142, 0xA>(v);
+  v += dpp_f32<0x143, 0xC>(v);
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace dr

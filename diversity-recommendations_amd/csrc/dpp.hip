@@ -36,42 +36,9 @@ constexpr int kMaxK = 128;               // picks (basis rows) per user
 using dr::bf16x8;
 using dr::f32x4;
 
-// DPP lane moves (VALU, no LDS round trip): quad swaps, half-row and row
-// mirrors, then row_bcast15 / 31 carry the running result into lane 63.
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {  // v itself in masked-out rows
-  const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
-  const int nlo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xF, false);
-  const int nhi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xF, false);
-  return ((uint64_t)(uint32_t)nhi << 32) | (uint32_t)nlo;
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-  v = dr::umax64(v, dpp_u64<0xB1>(v));        // quad_perm [1,0,3,2]
-  v = dr::umax64(v, dpp_u64<0x4E>(v));        // quad_perm [2,3,0,1]
-  v = dr::umax64(v, dpp_u64<0x141>(v));       // row_half_mirror
-  v = dr::umax64(v, dpp_u64<0x140>(v));       // row_mirror: every lane holds its row's max
-  v = dr::umax64(v, dpp_u64<0x142, 0xA>(v));  // row_bcast15 into rows 1 and 3
-  v = dr::umax64(v, dpp_u64<0x143, 0xC>(v));  // row_bcast31 into rows 2 and 3
-  return dr::readlane_u64(v, 63);
-}
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float dpp_f32(float v) {  // 0 in masked-out rows
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
-}
-__device__ __forceinline__ float quad_sum_f32(float v) {  // every lane: its quad's sum
-  v += dpp_f32<0xB1>(v);
-  v += dpp_f32<0x4E>(v);
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f32(float v) {  // uniform: the wave's sum
-  v = quad_sum_f32(v);
-  v += dpp_f32<0x141>(v);
-  v += dpp_f32<0x140>(v);
-  v += dpp_f32<0x142, 0xA>(v);
-  v += dpp_f32<0x143, 0xC>(v);
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
+// the DPP wave reductions of common.h
+using dr::quad_sum_f32;
+using dr::wave_max_u64;
 
 __device__ __forceinline__ float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
@@ -270,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void dpp_pick_kernel(
           split[tid] = (uint16_t)(hi >> 16);
           split[D + tid] = (uint16_t)(mid >> 16);
           split[2 * D + tid] = (uint16_t)(__float_as_uint(x2) >> 16);
-          const float sq = wave_sum_f32(x * x);
+          const float sq = dr::wave_sum_dpp_f32(x * x);
           if (lane == 0) s_nsq[w] = sq;
         }
         __syncthreads();

@@ -36,36 +36,12 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 using dr::bf16x8;
 using dr::f32x16;
 
-// Wave-wide max of a 64-bit key through DPP (VALU lane moves, no LDS round
-// trip): quad swaps, half-row and row mirrors, then the row_bcast15/31 steps
-// carry the running max into lane 63. The fast rounds are a serial chain of
-// these reductions, so their latency is the round time.
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {
-  const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
-  const int nlo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xF, false);
-  const int nhi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xF, false);
-  return ((uint64_t)(uint32_t)nhi << 32) | (uint32_t)nlo;
-}
-__device__ __forceinline__ uint32_t wave_min_u32_64(uint32_t v) {
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x142, 0xA, 0xF, false));
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x143, 0xC, 0xF, false));
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-  v = dr::umax64(v, dpp_u64<0xB1>(v));        // quad_perm [1,0,3,2]
-  v = dr::umax64(v, dpp_u64<0x4E>(v));        // quad_perm [2,3,0,1]
-  v = dr::umax64(v, dpp_u64<0x141>(v));       // row_half_mirror
-  v = dr::umax64(v, dpp_u64<0x140>(v));       // row_mirror: every lane holds its row's max
-  v = dr::umax64(v, dpp_u64<0x142, 0xA>(v));  // row_bcast15 into rows 1 and 3
-  v = dr::umax64(v, dpp_u64<0x143, 0xC>(v));  // row_bcast31 into rows 2 and 3
-  return dr::readlane_u64(v, 63);
-}
-
+// Wave-wide max of a 64-bit key through DPP (common.h): the fast rounds are a
+// serial chain of these reductions, so their latency is the round time.
+using dr::dpp_u64;
+using dr::wave_max_u64;
+using dr::wave_min_u32_64;
+using dr::wmax_u32;
 
 // a[lane] max a[lane ^ 32] (v_permlane32_swap: one VALU, no LDS round trip)
 __device__ __forceinline__ float half_swap_max(float x) {
@@ -86,24 +62,6 @@ __device__ unsigned long long g_mmr_diag[kWaves][16];
 #endif
 enum { kMgLoad, kMgSelect, kMgStage, kMgMma, kMgSync1, kMgRounds, kMgSync2, kMgFold, kMgBatches,
        kMgTotal, kMgStageBar, kMgGt, kMgSlots = 16 };
-
-// Max over the wave's 64 lanes (lanes = 64) or over lanes 0..31 (lanes = 32)
-// by fused v_max_u32_dpp steps (one VALU each: the reduction is the latency
-// of the serial chains below); the result is read from the last lane.
-template <int LANES>
-__device__ __forceinline__ uint32_t wmax_u32(uint32_t v) {
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true));
-  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, true));
-  if constexpr (LANES == 64) {
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, true));
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-  } else {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 31);
-  }
-}
 
 // ---------------------------------------------------------------------------
 // Round-3 layout: MFMA work proportional to the PICKS, not to the probes.

@@ -80,6 +80,10 @@ SIGNATURES = {
                             _p]),
     "dr_mmr_rerank": (_i32, [_p, _p, _i64, _i32, _p, _i64, _i32, _i32, _f32, _p, _p, _p]),
     "dr_dpp_rerank": (_i32, [_p, _p, _i64, _i32, _p, _i64, _i32, _i32, _f32, _p, _p, _p, _p]),
+    "dr_calibrated_rerank": (_i32, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _p,
+                                    _p]),
+    "dr_label_profile": (_i32, [_p, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "dr_calibration_kl": (_i32, [_p, _i32, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _p]),
     "dr_rank_metrics": (_i32, [_p, _i32, _i64, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "dr_catalog_histogram": (_i32, [_p, _i32, _i64, _i32, _i64, _p, _p, _p]),
 }

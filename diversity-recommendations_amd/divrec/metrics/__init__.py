@@ -6,6 +6,7 @@ from .average_precision_at_k import (
     MeanAveragePrecisionAtKScore,
     average_precision_at_k,
 )
+from .calibration_score import CalibrationScore
 from .entropy_diversity_score import EntropyDiversityScore
 from .normalized_discounted_cumulative_gain import NDCGScore, normalized_discounted_cumulative_gain
 from .popularity_rank_correlation_for_items import PRI, avg_rank, rank
@@ -15,6 +16,7 @@ from .recall_at_k import RecallAtKScore, recall_at_k
 __all__ = [
     "AUCScore",
     "AveragePrecisionAtKScore",
+    "CalibrationScore",
     "EntropyDiversityScore",
     "HitRateScore",
     "IntraListDiversityScore",

@@ -23,7 +23,8 @@ or raw pointers, which bump no autograd version, are always seen).
 
 ``recommend_diverse`` composes ``score_topk`` with a diversity re-rank of the
 top candidates (greedy DPP, dr_dpp_rerank, or MMR, dr_mmr_rerank) over the
-bf16 item table.
+bf16 item table, or with the calibrated re-rank over item partition labels
+(dr_calibrated_rerank).
 """
 from __future__ import annotations
 
@@ -36,8 +37,8 @@ from divrec import ops
 from .base_models import RankingModel
 
 PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16}
-RERANKERS = ("dpp", "mmr")    # recommend_diverse methods
-MAX_RERANK_CANDIDATES = 1024  # C of dr_dpp_rerank / dr_mmr_rerank
+RERANKERS = ("dpp", "mmr", "calibrated")  # recommend_diverse methods
+MAX_RERANK_CANDIDATES = 1024  # C of dr_dpp_rerank / dr_mmr_rerank / dr_calibrated_rerank
 
 
 class _GatherDot(torch.autograd.Function):
@@ -164,12 +165,21 @@ class MatrixFactorization(RankingModel):
         exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
         precision: str = "fp32",
         n_items: Optional[int] = None,
+        *,
+        item_labels: Optional[torch.Tensor] = None,
+        user_profile: Optional[torch.Tensor] = None,
+        n_labels: Optional[int] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Diversity re-ranked lists: the top-``candidates`` items of each user
         (``score_topk`` with the same ``user_ids`` / ``exclude`` / ``precision``
         / ``n_items``) re-ranked to ``k`` picks by ``method`` "dpp"
         (``ops.dpp_rerank``) or "mmr" (``ops.mmr_rerank``) at trade-off ``lam``
-        over the bf16 item table. Returns (items int64 [n, k] in pick order,
+        over the bf16 item table, or by "calibrated"
+        (``ops.calibrated_rerank``), which needs ``item_labels`` (int [catalog],
+        values in [0, G)) and ``user_profile`` (fp32 [n, G], one row per
+        listed user, e.g. ``ops.label_profile`` of the users' history;
+        ``n_labels``, when given, must equal G <= 64) and uses no item rows.
+        Returns (items int64 [n, k] in pick order,
         scores fp32 [n, k]: the picks' scan scores). A list that ends early
         (fewer eligible candidates than ``k``) holds item -1 / score -inf.
         ``k <= candidates <= min(1024, catalog)``, else ValueError."""
@@ -180,14 +190,35 @@ class MatrixFactorization(RankingModel):
         if not 1 <= k <= candidates <= min(MAX_RERANK_CANDIDATES, catalog):
             raise ValueError(f"need 1 <= k <= candidates <= min({MAX_RERANK_CANDIDATES}, catalog "
                              f"= {catalog}), got k = {k}, candidates = {candidates}")
+        if method == "calibrated":
+            if item_labels is None or user_profile is None:
+                raise ValueError('method "calibrated" needs item_labels and user_profile')
+            n_lists = self.no_users if user_ids is None else len(user_ids)
+            if user_profile.dim() != 2 or user_profile.size(0) != n_lists:
+                raise ValueError(f"user_profile must be [{n_lists}, n_labels], one row per user, "
+                                 f"got {tuple(user_profile.shape)}")
+            G = user_profile.size(1)
+            if n_labels is not None and int(n_labels) != G:
+                raise ValueError(f"n_labels = {n_labels}, but user_profile has {G} columns")
+            if not 1 <= G <= ops.CALIB_MAX_LABELS:
+                raise ValueError(f"need 1 <= n_labels <= {ops.CALIB_MAX_LABELS}, got {G}")
+            if item_labels.dim() != 1 or item_labels.size(0) < catalog:
+                raise ValueError(f"item_labels must hold a label for each of the {catalog} items")
+        elif item_labels is not None or user_profile is not None or n_labels is not None:
+            raise ValueError(f'item_labels, user_profile and n_labels belong to method '
+                             f'"calibrated", not {method!r}')
         cand, cand_scores = self.score_topk(candidates, user_ids=user_ids, exclude=exclude,
                                             precision=precision, n_items=n_items)
-        table = self.bf16_tables()[1][:catalog]
         cand32 = cand.to(torch.int32)
-        if method == "dpp":
-            picks, _ = ops.dpp_rerank(cand32, cand_scores, table, k, lam)
+        if method == "calibrated":
+            dev = cand.device
+            picks, _ = ops.calibrated_rerank(
+                cand32, cand_scores, item_labels[:catalog].to(dev),
+                user_profile.to(dev, torch.float32), k, lam)
+        elif method == "dpp":
+            picks, _ = ops.dpp_rerank(cand32, cand_scores, self.bf16_tables()[1][:catalog], k, lam)
         else:
-            picks = ops.mmr_rerank(cand32, cand_scores, table, k, lam)
+            picks = ops.mmr_rerank(cand32, cand_scores, self.bf16_tables()[1][:catalog], k, lam)
         picks = picks.to(torch.int64)
         # the picks' scan scores: candidate ids are distinct per user, so a pick
         # is found by a search in the user's sorted ids

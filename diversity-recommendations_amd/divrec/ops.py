@@ -738,6 +738,122 @@ def dpp_rerank(
     return out, resid
 
 
+# --------------------------------------------------------------------------- calibration
+CALIB_MAX_LABELS = 64  # DR_CALIB_MAX_LABELS
+
+
+def _labels32(labels: torch.Tensor) -> torch.Tensor:
+    """Item labels as the int32 table the calibration kernels read. int64
+    labels are clamped to [-1, 64] first, so a value no int32 holds stays
+    outside [0, G) instead of wrapping into it."""
+    _need(labels.dim() == 1 and labels.dtype in (torch.int32, torch.int64),
+          "item labels must be 1-D int32 or int64")
+    _need(labels.numel() >= 1, "item labels must not be empty")
+    if labels.dtype == torch.int64:
+        labels = labels.clamp(-1, CALIB_MAX_LABELS).to(torch.int32)
+    return labels.contiguous()
+
+
+def _n_labels(n_labels: int) -> int:
+    n_labels = int(n_labels)
+    _need(1 <= n_labels <= CALIB_MAX_LABELS, f"n_labels must be in [1, {CALIB_MAX_LABELS}]")
+    return n_labels
+
+
+def _profile(profile: torch.Tensor, n: int) -> torch.Tensor:
+    _need(profile.dtype == torch.float32 and profile.dim() == 2 and profile.size(0) == n,
+          "profile must be fp32 [n, n_labels]")
+    _n_labels(profile.size(1))
+    return profile.contiguous()
+
+
+def calibrated_rerank(
+    cand_items: torch.Tensor, cand_scores: torch.Tensor, item_labels: torch.Tensor,
+    profile: torch.Tensor, k_out: int, lam: float = 0.5, check: bool = True,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Greedy calibrated re-rank (Steck 2018) over per-user candidates (int32
+    [n, C] + fp32 [n, C]) -> (items int32 [n, k_out], kl fp32 [n, k_out]): each
+    pick maximises lam * score - (1 - lam) * KL(p || q~(list + pick)), p the
+    normalised row of ``profile`` (fp32 [n, G], G <= 64, e.g. ``label_profile``
+    of the user's history) and q~ the label shares of the list under
+    ``item_labels`` (int32 or int64 [n_items], values in [0, G)), smoothed with
+    p (include/divrec_hip.h). ``kl[:, t]`` is the list's KL after pick t, so
+    ``kl[:, -1]`` is ``calibration_kl`` of the finished list. A list that runs
+    out of live candidates ends in -1 with the KL repeated. Candidate ids < 0
+    are empty slots; with ``check`` a candidate id past the label table or a
+    candidate whose label is outside [0, G) raises IndexError after the call
+    (one counter read); without it such candidates are silently never picked."""
+    dev = B.require_device(cand_items, cand_scores, item_labels, profile)
+    _need(cand_items.dtype == torch.int32 and cand_scores.dtype == torch.float32,
+          "int32 candidate ids, fp32 scores")
+    _need(cand_items.dim() == 2 and cand_items.shape == cand_scores.shape, "[n, C] inputs")
+    n, C = cand_items.shape
+    labels, profile = _labels32(item_labels), _profile(profile, n)
+    out = torch.empty((n, int(k_out)), dtype=torch.int32, device=dev)
+    kl = torch.empty((n, int(k_out)), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out, kl
+    err = B.error_counter(dev) if check else None
+    rc = B.lib().dr_calibrated_rerank(
+        cand_items.contiguous().data_ptr(), cand_scores.contiguous().data_ptr(), n, C,
+        labels.data_ptr(), labels.numel(), profile.size(1), profile.data_ptr(), int(k_out),
+        float(lam), out.data_ptr(), kl.data_ptr(), B.ptr(err), B.stream(dev),
+    )
+    B.check(rc, "dr_calibrated_rerank")
+    B.raise_if_out_of_range(err, "dr_calibrated_rerank")
+    return out, kl
+
+
+def label_profile(rowptr: torch.Tensor, items: torch.Tensor, item_labels: torch.Tensor,
+                  n_labels: int, check: bool = True) -> torch.Tensor:
+    """fp32 [n, n_labels]: the normalised label histogram of every row of the
+    CSR (rowptr int64 [n + 1], items int32), the profile ``calibrated_rerank``
+    and ``calibration_kl`` take; an empty row is a zero row. With ``check`` an
+    item outside the label table or a label outside [0, n_labels) raises
+    IndexError (one counter read); without it they are skipped."""
+    dev = B.require_device(rowptr, items, item_labels)
+    _need(rowptr.dtype == torch.int64 and rowptr.dim() == 1 and rowptr.numel() >= 1,
+          "rowptr int64 [n + 1]")
+    _need(items.dtype == torch.int32 and items.dim() == 1, "items must be int32 1-D")
+    G, labels = _n_labels(n_labels), _labels32(item_labels)
+    n = rowptr.numel() - 1
+    out = torch.empty((n, G), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    err = B.error_counter(dev) if check else None
+    rc = B.lib().dr_label_profile(
+        rowptr.contiguous().data_ptr(), items.contiguous().data_ptr() if items.numel() else None,
+        n, labels.data_ptr(), labels.numel(), G, out.data_ptr(), B.ptr(err), B.stream(dev),
+    )
+    B.check(rc, "dr_label_profile")
+    B.raise_if_out_of_range(err, "dr_label_profile")
+    return out
+
+
+def calibration_kl(recs: torch.Tensor, item_labels: torch.Tensor, profile: torch.Tensor,
+                   check: bool = True) -> torch.Tensor:
+    """fp32 [n]: KL(p || q~) of each list of ``recs`` [n, k] (int32 or int64;
+    entries < 0, the tail of a list that ended early, are skipped) against the
+    normalised rows of ``profile`` (fp32 [n, G]); 0 is a perfectly calibrated
+    list. With ``check`` an entry past the label table or with a label outside
+    [0, G) raises IndexError (one counter read); without it it is skipped."""
+    dev = B.require_device(recs, item_labels, profile)
+    recs, rc_dt = _recs(recs)
+    n, k = recs.shape
+    labels, profile = _labels32(item_labels), _profile(profile, n)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    err = B.error_counter(dev) if check else None
+    rc = B.lib().dr_calibration_kl(
+        recs.data_ptr() if k else None, rc_dt, n, k, labels.data_ptr(), labels.numel(),
+        profile.size(1), profile.data_ptr(), out.data_ptr(), B.ptr(err), B.stream(dev),
+    )
+    B.check(rc, "dr_calibration_kl")
+    B.raise_if_out_of_range(err, "dr_calibration_kl")
+    return out
+
+
 # --------------------------------------------------------------------------- rank metrics
 def rank_metrics(
     recs: torch.Tensor, pos_rowptr: torch.Tensor, pos_items: torch.Tensor

@@ -42,6 +42,7 @@ from divrec.losses import (
 )
 from divrec.metrics import AUCScore
 from divrec.metrics import _rank
+from divrec.metrics.calibration_score import partition_labels
 from divrec.models import MatrixFactorization, RankingModel
 from divrec.models.matrix_factorization import MAX_RERANK_CANDIDATES, RERANKERS
 
@@ -184,15 +185,22 @@ def get_model_recommendations(dataset: RankingDataset, model: RankingModel,
 
 def get_diverse_recommendations(dataset: RankingDataset, model: RankingModel,
                                 number_of_recommendations: int, candidates: int,
-                                method: str = "dpp", lam: float = 0.5) -> torch.LongTensor:
+                                method: str = "dpp", lam: float = 0.5,
+                                items_partition_feature: str = "partition") -> torch.LongTensor:
     """Diversity re-ranked lists of every user of ``dataset`` (LongTensor
     [U, k] on the CPU, not in the reference): the top-``candidates``
     candidates of ``get_model_recommendations``' scan (fp32 scores, frozen
     items excluded) re-ranked to ``number_of_recommendations`` picks by
     ``MatrixFactorization.recommend_diverse`` (``method`` "dpp" or "mmr",
-    trade-off ``lam``). ValueError for a model outside the MF fast path, for
-    ragged candidate lists (as ``get_model_recommendations``) and for a list
-    that ends early (fewer eligible candidates than picks)."""
+    trade-off ``lam``). ``method`` "calibrated" re-ranks towards each user's
+    own mix of item partitions instead: the labels are
+    ``dataset.data.item_features[items_partition_feature]`` (at most 64 of
+    them), the user's profile the label histogram of its ``frozen`` items, its
+    history (``ops.label_profile`` over ``dataset.exclusion_csr()``).
+    ValueError for a model outside the MF fast path, for ragged candidate
+    lists (as ``get_model_recommendations``), for a list that ends early
+    (fewer eligible candidates than picks) and, for "calibrated", without
+    ``frozen`` or without the feature."""
     k, cands = int(number_of_recommendations), int(candidates)
     if method not in RERANKERS:
         raise ValueError(f"method must be one of {sorted(RERANKERS)}, got {method!r}")
@@ -207,12 +215,26 @@ def get_diverse_recommendations(dataset: RankingDataset, model: RankingModel,
     if n_users == 0:
         return torch.LongTensor([])
     excl = dataset.exclusion_csr()
+    labels = None
+    if method == "calibrated":
+        labels = partition_labels(dataset.data, items_partition_feature)
+        if excl is None:
+            raise ValueError('method "calibrated" takes the users\' profiles from the frozen '
+                             'interactions: the dataset has none')
     c_len = _list_length(dataset, excl, n_users, n_items, cands)
     if c_len < k:
         raise ValueError(f"a user has {c_len} candidates, fewer than the {k} recommendations asked for")
     user_ids = None if n_users == model.no_users else torch.arange(n_users)
+    calibrated = {}
+    if labels is not None:
+        dev, n_labels = model._device(), int(labels.max()) + 1
+        labels = labels.to(dev)
+        # the labels are validated above; a frozen item outside the catalog has none and is skipped
+        profile = ops.label_profile(excl[0].to(dev), excl[1].to(dev), labels, n_labels,
+                                    check=False)
+        calibrated = dict(item_labels=labels, user_profile=profile)
     items, _ = model.recommend_diverse(k, c_len, method=method, lam=lam, user_ids=user_ids,
-                                       exclude=excl, n_items=n_items)
+                                       exclude=excl, n_items=n_items, **calibrated)
     items = items.cpu()
     if bool((items < 0).any()):
         short = int((items < 0).any(dim=1).sum())

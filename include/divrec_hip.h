@@ -52,7 +52,7 @@ const char* dr_build_id(void);
 const char* dr_last_error(void);
 
 /* Planner knobs: process-wide overrides of dr_score_topk's launch planner (and
- * of dr_mmr_rerank's and dr_dpp_rerank's grids, DR_KNOB_SCAN_SLOTS), for tests and A/B timing runs
+ * of dr_mmr_rerank's, dr_dpp_rerank's and dr_calibrated_rerank's grids, DR_KNOB_SCAN_SLOTS), for tests and A/B timing runs
  * only. Every plan gives identical results; only the time differs. The
  * library reads no environment variable: a knob holds the default plan until
  * it is set here, and value NaN restores the default. Thread-safe (atomic). */
@@ -432,6 +432,65 @@ int dr_mmr_rerank(const int32_t* cand_items, const float* cand_scores, int64_t n
 int dr_dpp_rerank(const int32_t* cand_items, const float* cand_scores, int64_t n_users, int C,
                   const void* item_table, int64_t n_items, int d, int k_out, float lambda,
                   int32_t* out_items, float* out_resid, int32_t* err, dr_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Calibrated re-rank over item partition labels (Steck, "Calibrated
+ * Recommendations", RecSys 2018; no reference symbol, as for MMR and DPP; the
+ * labels are the reference's item_features["partition"], the surface of
+ * IntraListBinaryUnfairnessScore, intra_list_diversity_score.py:45-63). Per
+ * user: a profile row w[G] (fp32), normalised to p_g = max(w_g, 0) / sum_g
+ * max(w_g, 0) (NaN counts as 0; a row whose sum is 0 gives p = 0, so every KL
+ * below is 0; weights must be finite), labels l(i) in [0, G), and after t
+ * picks the label counts n_g. For a candidate of label c
+ *   q~_g(c) = (1 - alpha) (n_g + [g = c]) / (t + 1) + alpha p_g
+ *   KL_c    = sum_{g : p_g > 0} p_g log(p_g / q~_g(c))     (finite: q~_g >= alpha p_g)
+ *   value_i = lambda * score_i - (1 - lambda) * KL_{l(i)}
+ * and each step picks the live candidate of highest value (ties -> lowest
+ * candidate position), then n_{l(pick)} += 1. lambda = 1, G = 1 and a zero
+ * profile row each give the stable order by score. cand_items int32
+ * [n_users, C], cand_scores fp32 [n_users, C] (-inf and NaN count as -FLT_MAX),
+ * item_labels int32 [n_items], profile fp32 [n_users, G]; out_items int32
+ * [n_users, k_out] (item ids in selection order), out_kl fp32 [n_users, k_out]
+ * (may be NULL): KL(p || q~) of the list after each pick.
+ * Never live, never picked: candidate ids < 0 (empty slots); ids >= n_items
+ * (added to *err, an int32 device counter that may be NULL; their label is
+ * never read); candidates whose label is outside [0, G) (added to *err).
+ * Positions are picked once each; duplicate ids are not detected. When no live
+ * candidate is left the remaining picks are -1 and out_kl repeats the KL of
+ * the list as it stands (-log(alpha) [sum p > 0] for an empty list), so
+ * out_kl[:, k_out - 1] is the finished list's dr_calibration_kl.
+ * 1 <= C <= 1024 and 1 <= G <= DR_CALIB_MAX_LABELS (above: DR_EUNSUPPORTED),
+ * 1 <= k_out <= C, lambda in [0, 1]; n_items = 0 is DR_EINVAL.
+ * Launch: one wave per user (lane g = category g, 16 candidates per lane),
+ * four users per workgroup, a persistent grid (DR_KNOB_SCAN_SLOTS caps it, as
+ * for dr_mmr_rerank). */
+#define DR_CALIB_ALPHA 0.01f
+#define DR_CALIB_MAX_LABELS 64
+int dr_calibrated_rerank(const int32_t* cand_items, const float* cand_scores, int64_t n_users,
+                         int C, const int32_t* item_labels, int64_t n_items, int G,
+                         const float* profile, int k_out, float lambda, int32_t* out_items,
+                         float* out_kl, int32_t* err, dr_stream_t stream);
+
+/* Profiles for dr_calibrated_rerank from a history CSR (rowptr int64
+ * [n_rows + 1], items int32; the exclusion CSR of dr_score_topk is one):
+ * out[r, g] = (items of row r with label g) / (items of row r with a valid
+ * label), fp32 [n_rows, G]; an empty row is a zero row. Items outside
+ * [0, n_items) and labels outside [0, G) are skipped and counted in *err.
+ * The counts are exact integers (rows of fewer than 2^24 items) and the value
+ * is one fp32 divide of the two. Limits of G and n_items as above. */
+int dr_label_profile(const int64_t* rowptr, const int32_t* items, int64_t n_rows,
+                     const int32_t* item_labels, int64_t n_items, int G, float* out, int32_t* err,
+                     dr_stream_t stream);
+
+/* Calibration of finished lists: out[u] = KL(p || q~), q~_g = (1 - alpha) q_g +
+ * alpha p_g, q_g the share of label g among the valid entries of recs[u, :]
+ * ([n_users, k], rec_dtype DR_I32 or DR_I64) and p the normalised profile row,
+ * as above. Entries < 0 (a list that ended early) are skipped; entries >=
+ * n_items or with a label outside [0, G) are skipped and counted in *err. A
+ * list without a valid entry has q = 0: -log(alpha) [sum p > 0]. */
+int dr_calibration_kl(const void* recs, int rec_dtype, int64_t n_users, int k,
+                      const int32_t* item_labels, int64_t n_items, int G, const float* profile,
+                      float* out, int32_t* err, dr_stream_t stream);
 
 #ifdef __cplusplus
 }
