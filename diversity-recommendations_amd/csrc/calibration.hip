@@ -22,6 +22,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "rerank_args.h"
 
 namespace {
 
@@ -228,19 +229,16 @@ __global__ __launch_bounds__(kThreads) void calibration_kl_kernel(
 
 // Persistent grid of one-wave workers: as many workgroups per CU as are
 // resident at once (the kernel's own occupancy; 4 if the query fails), each
-// wave looping over the units (users, rows). DR_KNOB_SCAN_SLOTS caps the CUs
-// planned for, as for dr_mmr_rerank, so tests reach many users per wave with
-// few users.
+// wave looping over the units (users, rows). The CUs planned for are
+// dr::persistent_cus(), so the DR_KNOB_SCAN_SLOTS cap applies as for
+// dr_mmr_rerank and tests reach many users per wave with few users.
 template <typename Kernel>
 dim3 wave_grid(Kernel kernel, int64_t units) {
-  int cus = dr::device_cus();
-  double v;
-  if (dr::plan_knob(DR_KNOB_SCAN_SLOTS, &v) && v > 0 && (int)v < cus) cus = (int)v;
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, 0) != hipSuccess ||
       per_cu < 1)
     per_cu = 4;
-  const int64_t need = dr::ceil_div(units, kWaves), cap = (int64_t)cus * per_cu;
+  const int64_t need = dr::ceil_div(units, kWaves), cap = (int64_t)dr::persistent_cus() * per_cu;
   return dim3((unsigned)(need < cap ? need : cap));
 }
 
@@ -268,15 +266,10 @@ extern "C" int dr_calibrated_rerank(const int32_t* cand_items, const float* cand
                                     int64_t n_items, int G, const float* profile, int k_out,
                                     float lambda, int32_t* out_items, float* out_kl, int32_t* err,
                                     dr_stream_t stream) {
-  DR_CHECK_ARG(n_users >= 0, "n_users must be >= 0");
-  if (C > kMaxC) {
-    dr::set_error("dr_calibrated_rerank: C must be <= 1024");
-    return DR_EUNSUPPORTED;
-  }
-  DR_CHECK_ARG(C >= 1, "C must be >= 1");
-  DR_CHECK_ARG(k_out >= 1 && k_out <= C, "k_out must be in [1, C]");
-  DR_CHECK_ARG(lambda >= 0.f && lambda <= 1.f, "lambda must be in [0, 1]");
-  if (const int rc = check_labels(__func__, n_items, G)) return rc;
+  static_assert(kMaxC == dr::kRerankMaxC, "the shared check's bound");
+  DR_CHECK_RC(
+      dr::check_candidates(__func__, n_users, C, k_out, lambda, dr::kCalibratedArgs));
+  DR_CHECK_RC(check_labels(__func__, n_items, G));
   if (n_users == 0) return DR_OK;
   DR_CHECK_ARG(cand_items && cand_scores && item_labels && profile && out_items, "null pointer");
   hipLaunchKernelGGL(calib_pick_kernel, wave_grid(calib_pick_kernel, n_users), dim3(kThreads), 0,
@@ -290,7 +283,7 @@ extern "C" int dr_label_profile(const int64_t* rowptr, const int32_t* items, int
                                 const int32_t* item_labels, int64_t n_items, int G, float* out,
                                 int32_t* err, dr_stream_t stream) {
   DR_CHECK_ARG(n_rows >= 0, "n_rows must be >= 0");
-  if (const int rc = check_labels(__func__, n_items, G)) return rc;
+  DR_CHECK_RC(check_labels(__func__, n_items, G));
   if (n_rows == 0) return DR_OK;
   DR_CHECK_ARG(rowptr && item_labels && out, "null pointer");  // items may be NULL: all rows empty
   hipLaunchKernelGGL(label_profile_kernel, wave_grid(label_profile_kernel, n_rows), dim3(kThreads), 0,
@@ -305,7 +298,7 @@ extern "C" int dr_calibration_kl(const void* recs, int rec_dtype, int64_t n_user
                                  dr_stream_t stream) {
   DR_CHECK_ARG(n_users >= 0 && k >= 0, "n_users and k must be >= 0");
   DR_CHECK_ARG(rec_dtype == DR_I32 || rec_dtype == DR_I64, "recs must be DR_I32 or DR_I64");
-  if (const int rc = check_labels(__func__, n_items, G)) return rc;
+  DR_CHECK_RC(check_labels(__func__, n_items, G));
   if (n_users == 0) return DR_OK;
   DR_CHECK_ARG((recs || k == 0) && item_labels && profile && out, "null pointer");
   hipStream_t s = (hipStream_t)stream;

@@ -64,6 +64,13 @@ int device_cus() {
   }
   return n;
 }
+
+int persistent_cus() {
+  int cus = device_cus();
+  double v;
+  if (plan_knob(DR_KNOB_SCAN_SLOTS, &v) && v > 0 && (int)v < cus) cus = (int)v;
+  return cus;
+}
 }  // namespace dr
 
 extern "C" int dr_set_plan_knob(int knob, double value) {

@@ -24,6 +24,13 @@ bool plan_knob(int id, double* v);
 // query fails): the grid of the persistent kernels.
 int device_cus();
 
+// device_cus() CAPPED by the DR_KNOB_SCAN_SLOTS test knob (applied when it is
+// below the count): the grid of the re-rank kernels, so that tests reach many
+// users per workgroup with few users. The score scan's planner reads the same
+// knob as an OVERRIDE (score_topk.hip, scan_slots()): a value above the device's
+// count is honoured there too, which is how plans for a larger device are tested.
+int persistent_cus();
+
 #define DR_CHECK_ARG(cond, msg)                                   \
   do {                                                            \
     if (!(cond)) {                                                \

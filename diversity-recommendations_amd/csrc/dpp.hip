@@ -23,6 +23,7 @@
 // A step is a serial chain (argmax -> stage -> 2 x project -> pass), so its
 // reductions run on DPP lane moves, not LDS round trips.
 #include "common.h"
+#include "rerank_args.h"
 
 namespace {
 
@@ -303,27 +304,18 @@ extern "C" int dr_dpp_rerank(const int32_t* cand_items, const float* cand_scores
                              int C, const void* item_table, int64_t n_items, int d, int k_out,
                              float lambda, int32_t* out_items, float* out_resid, int32_t* err,
                              dr_stream_t stream) {
-  DR_CHECK_ARG(n_users >= 0, "n_users must be >= 0");
-  DR_CHECK_ARG(C >= 1 && C <= kMaxC, "C must be in [1, 1024]");
-  DR_CHECK_ARG(k_out >= 1 && k_out <= C && k_out <= kMaxK, "k_out must be in [1, min(C, 128)]");
-  DR_CHECK_ARG(lambda >= 0.f && lambda <= 1.f, "lambda must be in [0, 1]");
-  DR_CHECK_ARG(n_items >= 0 && n_items < 0x7fffffffLL, "n_items must be in [0, 2^31)");
-  if (d != 64 && d != 128) {
-    dr::set_error("dr_dpp_rerank: d must be 64 or 128");
-    return DR_EUNSUPPORTED;
-  }
+  static_assert(kMaxC == dr::kRerankMaxC && kMaxK == dr::kDppArgs.max_k,
+                "the shared check's bounds");
+  DR_CHECK_RC(dr::check_candidates(__func__, n_users, C, k_out, lambda, dr::kDppArgs));
+  DR_CHECK_RC(dr::check_item_rows(__func__, n_items));
+  DR_CHECK_RC(dr::check_item_width(__func__, d));  // before the n_users == 0 exit, unlike MMR
   if (n_users == 0) return DR_OK;
-  if (n_items == 0) {  // no row a candidate could name (the kernel reads row 0 for empty slots)
-    dr::set_error("dr_dpp_rerank: empty item table");
-    return DR_EINVAL;
-  }
+  DR_CHECK_RC(dr::check_item_table_filled(__func__, n_items));
   DR_CHECK_ARG(cand_items && cand_scores && item_table && out_items, "null pointer");
   hipStream_t s = (hipStream_t)stream;
   // persistent grid: one workgroup per CU (a user's rows take half the register
-  // file), each looping over users; DR_KNOB_SCAN_SLOTS caps it for tests
-  int cus = dr::device_cus();
-  double v;
-  if (dr::plan_knob(DR_KNOB_SCAN_SLOTS, &v) && v > 0 && (int)v < cus) cus = (int)v;
+  // file), each looping over users
+  const int cus = dr::persistent_cus();
   const dim3 grid((unsigned)(n_users < cus ? n_users : cus));
 #define DR_DPP(DD)                                                                             \
   hipLaunchKernelGGL(dpp_pick_kernel<DD>, grid, dim3(kThreads), 0, s, cand_items, cand_scores,  \

@@ -19,10 +19,9 @@
 //     greedy's.
 //   * When no probe beats BOUND the batch ends: one MFMA pass of the batch's
 //     picks against every candidate folds their cosines into the max terms.
-#include <atomic>
-#include <cstdlib>
 
 #include "common.h"
+#include "rerank_args.h"
 
 namespace {
 
@@ -752,55 +751,28 @@ extern "C" int dr_mmr_diag_read(unsigned long long* out, int reset) {
 namespace {
 #endif
 
-// CUs of the current device (cached per device ordinal: a process may drive
-// GPUs of different sizes); DR_KNOB_SCAN_SLOTS, the planner's test knob, caps
-// the grid so that tests reach many users per workgroup with few users.
-int grid_cus() {
-  static std::atomic<int> cache[64];
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-  if (dev >= 0 && dev < 64) n = cache[dev].load(std::memory_order_relaxed);
-  if (n <= 0) {
-    if (dev < 0 || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
-                       hipSuccess || n <= 0)
-      n = 256;
-    if (dev >= 0 && dev < 64) cache[dev].store(n, std::memory_order_relaxed);
-  }
-  double v;
-  if (dr::plan_knob(DR_KNOB_SCAN_SLOTS, &v) && v > 0 && (int)v < n) n = (int)v;
-  return n;
-}
-
 }  // namespace
 
 extern "C" int dr_mmr_rerank(const int32_t* cand_items, const float* cand_scores, int64_t n_users,
                              int C, const void* item_table, int64_t n_items, int d, int k_out,
                              float lambda, int32_t* out_items, int32_t* err, dr_stream_t stream) {
-  DR_CHECK_ARG(C >= 1 && C <= kMaxC, "C must be in [1, 1024]");
-  DR_CHECK_ARG(k_out >= 1 && k_out <= C, "k_out must be in [1, C]");
-  DR_CHECK_ARG(lambda >= 0.f && lambda <= 1.f, "lambda must be in [0, 1]");
-  DR_CHECK_ARG(n_items >= 0 && n_items < 0x7fffffffLL, "n_items must be in [0, 2^31)");
+  // n_users is not looked at, and d only after the pointers (rerank_args.h)
+  static_assert(kMaxC == dr::kRerankMaxC, "the shared check's bound");
+  DR_CHECK_RC(dr::check_candidates(__func__, n_users, C, k_out, lambda, dr::kMmrArgs));
+  DR_CHECK_RC(dr::check_item_rows(__func__, n_items));
   if (n_users == 0) return DR_OK;
-  if (n_items == 0) {  // no row a candidate could name (the kernel reads row 0 for empty slots)
-    dr::set_error("dr_mmr_rerank: empty item table");
-    return DR_EINVAL;
-  }
+  DR_CHECK_RC(dr::check_item_table_filled(__func__, n_items));
   DR_CHECK_ARG(cand_items && cand_scores && item_table && out_items, "null pointer");
+  DR_CHECK_RC(dr::check_item_width(__func__, d));
   hipStream_t s = (hipStream_t)stream;
   // persistent grid: one workgroup per CU (a user's rows take half the
   // register file), each looping over users and prefetching the next one
-  const int cus = grid_cus();
+  const int cus = dr::persistent_cus();
   const dim3 grid((unsigned)(n_users < cus ? n_users : cus));
 #define DR_MMR(DD)                                                                            \
   hipLaunchKernelGGL(mmr_pick_kernel<DD>, grid, dim3(kThreads), 0, s, cand_items, cand_scores,  \
                      C, (const __bf16*)item_table, n_items, n_users, k_out, lambda, out_items, err)
-  switch (d) {
-    case 64: DR_MMR(64); break;
-    case 128: DR_MMR(128); break;
-    default:
-      dr::set_error("dr_mmr_rerank: d must be 64 or 128");
-      return DR_EUNSUPPORTED;
-  }
+  if (d == 64) DR_MMR(64); else DR_MMR(128);
 #undef DR_MMR
   DR_CHECK_LAUNCH();
   return DR_OK;

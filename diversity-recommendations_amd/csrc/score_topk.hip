@@ -447,14 +447,9 @@ int knob_int(int id, int fallback) {
   return dr::plan_knob(id, &v) ? (int)v : fallback;
 }
 
-int device_cus() {
+int scan_slots() {  // an override, not the cap of dr::persistent_cus() (common.h)
   const int slots = knob_int(DR_KNOB_SCAN_SLOTS, 0);
-  if (slots > 0) return slots;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 256;
-  return cus > 0 ? cus : 256;
+  return slots > 0 ? slots : dr::device_cus();
 }
 
 int64_t stage_items_for(int w, int cap) {
@@ -528,7 +523,7 @@ Plan make_plan(int64_t n_users, int64_t n_items, int w, int k, bool seedable,
   p.users_per_wg = nut_for(w) * 32 * kWavesScan;
   p.n_ublocks = dr::ceil_div(n_users, p.users_per_wg);
   p.n_users_pad = p.n_ublocks * p.users_per_wg;
-  const int64_t slots = device_cus();
+  const int64_t slots = scan_slots();
   const int64_t stage_items = stage_items_for(w, p.cap);
   int max_c_override = 0;
   const int64_t B = p.n_ublocks;
@@ -718,7 +713,7 @@ Guess guess_for(int64_t n_items, int k, bool split_tail) {
 
 size_t diag_bytes() {
 #ifdef DR_TOPK_DIAG
-  return (size_t)device_cus() * kWavesScan * kDgSlots * sizeof(uint64_t);
+  return (size_t)scan_slots() * kWavesScan * kDgSlots * sizeof(uint64_t);
 #else
   return 0;
 #endif
@@ -1249,7 +1244,7 @@ extern "C" int dr_score_topk(const void* user_table, const int64_t* user_ids, in
     a2.buf_blocks = p.buf_rows / p.users_per_wg;
     a2.diag = nullptr;
     Plan p2 = p;
-    p2.grid = device_cus();
+    p2.grid = scan_slots();
     DR_TRY(run_scan(fn, p2, a2, dtype, w, true, s));
     const DevSplitArgs dsa{p.users_per_wg, p2.grid, kMaxRescanChunks,
                            a2.buf_blocks,  n_items, stage_items_for(w, p.cap)};

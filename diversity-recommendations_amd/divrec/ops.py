@@ -25,6 +25,31 @@ def _need(cond: bool, msg: str) -> None:
         raise ValueError(msg)
 
 
+def _counter(dev: torch.device, err: Optional[torch.Tensor] = None, check: bool = True):
+    """(the id-range counter a call counts in, the one ``_done`` reads after
+    it): the caller's ``err`` and None when it gave one (it reads it when it
+    chooses), else with ``check`` twice a fresh counter, else None twice."""
+    own = B.error_counter(dev) if err is None and check else None
+    return (err if own is None else own), own
+
+
+def _done(rc: int, name: str, own: Optional[torch.Tensor] = None) -> None:
+    """A C call's return code, then its own id-range counter (one host sync), if any."""
+    B.check(rc, name)
+    B.raise_if_out_of_range(own, name)
+
+
+def _grad_like(grad: Optional[torch.Tensor], table: torch.Tensor, name: str) -> None:
+    if grad is not None:
+        _need(grad.shape == table.shape and grad.dtype == torch.float32 and grad.is_contiguous(),
+              f"{name} must be a contiguous fp32 tensor shaped like its table")
+
+
+def _user_ids(user_ids: torch.Tensor) -> torch.Tensor:
+    _need(user_ids.dtype == torch.int64 and user_ids.dim() == 1, "user_ids must be 1-D int64")
+    return user_ids.contiguous()
+
+
 # --------------------------------------------------------------------------- MF forward
 def gather_dot(
     user_table: torch.Tensor,
@@ -51,17 +76,13 @@ def gather_dot(
     _contig(user_table, "user_table"), _contig(item_table, "item_table")
     user_id, item_id = user_id.contiguous(), item_id.contiguous()
     out = torch.empty(user_id.numel(), dtype=torch.float32, device=dev)
-    own = err is None and check
-    if own:
-        err = B.error_counter(dev)
+    err, own = _counter(dev, err, check)
     rc = B.lib().dr_gather_dot(
         user_table.data_ptr(), user_table.size(0), item_table.data_ptr(), item_table.size(0),
         B.dtype_code(user_table.dtype), user_table.size(1), user_id.data_ptr(), item_id.data_ptr(),
         user_id.numel(), out.data_ptr(), B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_gather_dot")
-    if own:
-        B.raise_if_out_of_range(err, "dr_gather_dot")
+    _done(rc, "dr_gather_dot", own)
     return out
 
 
@@ -80,10 +101,7 @@ def gather_dot_backward(
     dev = B.require_device(user_table, item_table, user_id, item_id, grad_out, grad_user, grad_item)
     _need(user_table.dtype == torch.float32 and item_table.dtype == torch.float32,
           "backward needs fp32 tables")
-    for g, t, nm in ((grad_user, user_table, "grad_user"), (grad_item, item_table, "grad_item")):
-        if g is not None:
-            _need(g.shape == t.shape and g.dtype == torch.float32 and g.is_contiguous(),
-                  f"{nm} must be a contiguous fp32 tensor shaped like its table")
+    _grad_like(grad_user, user_table, "grad_user"), _grad_like(grad_item, item_table, "grad_item")
     grad_out = grad_out.to(torch.float32).contiguous()
     rc = B.lib().dr_gather_dot_backward(
         user_table.data_ptr(), user_table.size(0), item_table.data_ptr(), item_table.size(0),
@@ -168,8 +186,7 @@ def score_topk(
     user_table, item_table = pad_columns(user_table, w), pad_columns(item_table, w)
     _need(1 <= k <= 1024, "k must be in [1, 1024]")
     if user_ids is not None:
-        _need(user_ids.dtype == torch.int64 and user_ids.dim() == 1, "user_ids must be 1-D int64")
-        user_ids = user_ids.contiguous()
+        user_ids = _user_ids(user_ids)
         n = user_ids.numel()
         if n:
             lo, hi = int(user_ids.min()), int(user_ids.max())
@@ -268,8 +285,7 @@ def sample_thresholds(user_table: torch.Tensor, sample_rows: torch.Tensor, ks1: 
     user_table = pad_columns(user_table, w)
     sample_rows = pad_columns(sample_rows.contiguous(), w)
     if user_ids is not None:
-        _need(user_ids.dtype == torch.int64 and user_ids.dim() == 1, "user_ids must be 1-D int64")
-        user_ids = user_ids.contiguous()
+        user_ids = _user_ids(user_ids)
         n = user_ids.numel()
     else:
         n = user_table.size(0)
@@ -318,50 +334,42 @@ def _recs(recs: torch.Tensor) -> Tuple[torch.Tensor, int]:
     return recs.contiguous(), B.dtype_code(recs.dtype)
 
 
-def ild_dense(recs: torch.Tensor, dist: torch.Tensor) -> torch.Tensor:
-    """Per-user ILD against a dense [I, I] distance matrix (fp32/fp64/int32/int64)."""
-    dev = B.require_device(recs, dist)
-    recs, rc_dt = _recs(recs)
+def _dist_matrix(dist: torch.Tensor) -> torch.Tensor:
     _need(dist.dim() == 2 and dist.size(0) == dist.size(1), "distance matrix must be [I, I]")
     _need(dist.dtype in (torch.float32, torch.float64, torch.int32, torch.int64),
           "distance matrix dtype must be float32/float64/int32/int64")
-    dist = dist.contiguous()
+    return dist.contiguous()
+
+
+def _ild_dense(recs: torch.Tensor, dist: torch.Tensor, symbol: str,
+               out_dtype: torch.dtype) -> torch.Tensor:
+    """The two dense-matrix ILD calls: one C signature, two symbols and output types."""
+    dev = B.require_device(recs, dist)
+    recs, rc_dt = _recs(recs)
+    dist = _dist_matrix(dist)
     n, k = recs.shape
-    out = torch.empty(n, dtype=torch.float32, device=dev)
+    out = torch.empty(n, dtype=out_dtype, device=dev)
     if n == 0:
         return out
-    err = B.error_counter(dev)
-    rc = B.lib().dr_ild_dense(
+    err, own = _counter(dev)
+    rc = getattr(B.lib(), symbol)(
         recs.data_ptr(), rc_dt, n, k, dist.data_ptr(), B.dtype_code(dist.dtype), dist.size(0),
         out.data_ptr(), err.data_ptr(), B.stream(dev),
     )
-    B.check(rc, "dr_ild_dense")
-    B.raise_if_out_of_range(err, "dr_ild_dense")
+    _done(rc, symbol, own)
     return out
+
+
+def ild_dense(recs: torch.Tensor, dist: torch.Tensor) -> torch.Tensor:
+    """Per-user ILD against a dense [I, I] distance matrix (fp32/fp64/int32/int64)."""
+    return _ild_dense(recs, dist, "dr_ild_dense", torch.float32)
 
 
 def ild_dense_pair_sum(recs: torch.Tensor, dist: torch.Tensor) -> torch.Tensor:
     """Per-user UN-normalised pair sum sum_{p<q} D[r_p, r_q] (the reference's
     user_ild), accumulated in D's precision; float64 [n] (exact for fp32 and
     integer D)."""
-    dev = B.require_device(recs, dist)
-    recs, rc_dt = _recs(recs)
-    _need(dist.dim() == 2 and dist.size(0) == dist.size(1), "distance matrix must be [I, I]")
-    _need(dist.dtype in (torch.float32, torch.float64, torch.int32, torch.int64),
-          "distance matrix dtype must be float32/float64/int32/int64")
-    dist = dist.contiguous()
-    n, k = recs.shape
-    out = torch.empty(n, dtype=torch.float64, device=dev)
-    if n == 0:
-        return out
-    err = B.error_counter(dev)
-    rc = B.lib().dr_ild_dense_pair_sum(
-        recs.data_ptr(), rc_dt, n, k, dist.data_ptr(), B.dtype_code(dist.dtype), dist.size(0),
-        out.data_ptr(), err.data_ptr(), B.stream(dev),
-    )
-    B.check(rc, "dr_ild_dense_pair_sum")
-    B.raise_if_out_of_range(err, "dr_ild_dense_pair_sum")
-    return out
+    return _ild_dense(recs, dist, "dr_ild_dense_pair_sum", torch.float64)
 
 
 def ild_labels(recs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
@@ -373,13 +381,12 @@ def ild_labels(recs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     out = torch.empty(n, dtype=torch.float32, device=dev)
     if n == 0:
         return out
-    err = B.error_counter(dev)
+    err, own = _counter(dev)
     rc = B.lib().dr_ild_labels(
         recs.data_ptr(), rc_dt, n, k, labels.data_ptr(), labels.numel(), out.data_ptr(),
         err.data_ptr(), B.stream(dev),
     )
-    B.check(rc, "dr_ild_labels")
-    B.raise_if_out_of_range(err, "dr_ild_labels")
+    _done(rc, "dr_ild_labels", own)
     return out
 
 
@@ -394,6 +401,20 @@ def _width_of(widths, d: int, what: str) -> int:
         if d <= w:
             return w
     raise ValueError(f"{what} supports embedding_dim <= {widths[-1]}, got {d}")
+
+
+def _bf16_rows(item_table: torch.Tensor, widths, what: str) -> torch.Tensor:
+    """A bf16 [rows, d] table, contiguous and zero-padded to the next of ``widths``."""
+    _need(item_table.dtype == torch.bfloat16 and item_table.dim() == 2, "item_table must be bf16 2-D")
+    return pad_columns(item_table.contiguous(), _width_of(widths, item_table.size(1), what))
+
+
+def _candidates(cand_items: torch.Tensor, cand_scores: torch.Tensor):
+    """The re-rankers' candidates, contiguous: (ids int32 [n, C], scores fp32 [n, C], n, C)."""
+    _need(cand_items.dtype == torch.int32 and cand_scores.dtype == torch.float32,
+          "int32 candidate ids, fp32 scores")
+    _need(cand_items.dim() == 2 and cand_items.shape == cand_scores.shape, "[n, C] inputs")
+    return cand_items.contiguous(), cand_scores.contiguous(), *cand_items.shape
 
 
 def ild_embedding(recs: torch.Tensor, item_table: torch.Tensor, kind: str = "cosine",
@@ -416,13 +437,12 @@ def ild_embedding(recs: torch.Tensor, item_table: torch.Tensor, kind: str = "cos
     out = torch.empty(n, dtype=torch.float32, device=dev)
     if n == 0:
         return out
-    err = B.error_counter(dev) if check else None
+    err, own = _counter(dev, check=check)
     rc = B.lib().dr_ild_embedding(
         recs.data_ptr(), rc_dt, n, k, item_table.data_ptr(), item_table.size(0),
         item_table.size(1), _KINDS[kind], out.data_ptr(), B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_ild_embedding")
-    B.raise_if_out_of_range(err, "dr_ild_embedding")
+    _done(rc, "dr_ild_embedding", own)
     return out
 
 
@@ -464,17 +484,13 @@ def ild_embedding_backward(
         grad_out = grad_out.to(torch.float32).contiguous()
     if n == 0:
         return
-    own = err is None and check
-    if own:
-        err = B.error_counter(dev)
+    err, own = _counter(dev, err, check)
     rc = B.lib().dr_ild_embedding_backward(
         recs.data_ptr(), rc_dt, n, k, item_table.data_ptr(), item_table.size(0),
         item_table.size(1), _KINDS[kind], B.ptr(grad_out), float(scale), grad_item.data_ptr(),
         B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_ild_embedding_backward")
-    if own:
-        B.raise_if_out_of_range(err, "dr_ild_embedding_backward")
+    _done(rc, "dr_ild_embedding_backward", own)
 
 
 # --------------------------------------------------------------------------- BPR
@@ -504,18 +520,14 @@ def bpr_fwd_bwd(
     n = user_id.numel()
     loss = torch.empty(n, dtype=torch.float32, device=dev)
     hit = torch.empty(n, dtype=torch.int32, device=dev)
-    own = err is None and check
-    if own:
-        err = B.error_counter(dev)
+    err, own = _counter(dev, err, check)
     rc = B.lib().dr_bpr_fwd_bwd(
         user_table.data_ptr(), user_table.size(0), item_table.data_ptr(), item_table.size(0),
         user_table.size(1), user_id.contiguous().data_ptr(), pos_id.contiguous().data_ptr(),
         neg_id.contiguous().data_ptr(), n, float(grad_scale), loss.data_ptr(), hit.data_ptr(),
         B.ptr(grad_user), B.ptr(grad_item), B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_bpr_fwd_bwd")
-    if own:
-        B.raise_if_out_of_range(err, "dr_bpr_fwd_bwd")
+    _done(rc, "dr_bpr_fwd_bwd", own)
     return loss, hit
 
 
@@ -552,25 +564,18 @@ def mse_fwd_bwd(
     n = user_id.numel()
     _need(target.dtype == torch.float32 and target.dim() == 1 and target.numel() == n,
           "target must be 1-D fp32, one per pair")
-    for g, t, nm in ((grad_user, user_table, "grad_user"), (grad_item, item_table, "grad_item")):
-        if g is not None:
-            _need(g.shape == t.shape and g.dtype == torch.float32 and g.is_contiguous(),
-                  f"{nm} must be a contiguous fp32 tensor shaped like its table")
+    _grad_like(grad_user, user_table, "grad_user"), _grad_like(grad_item, item_table, "grad_item")
     user_id, item_id, target = user_id.contiguous(), item_id.contiguous(), target.contiguous()
     pred = torch.empty(n, dtype=torch.float32, device=dev)
     loss = torch.empty(n, dtype=torch.float32, device=dev)
-    own = err is None and check
-    if own:
-        err = B.error_counter(dev)
+    err, own = _counter(dev, err, check)
     rc = B.lib().dr_mse_fwd_bwd(
         user_table.data_ptr(), user_table.size(0), item_table.data_ptr(), item_table.size(0),
         user_table.size(1), user_id.data_ptr(), item_id.data_ptr(),
         target.data_ptr(), n, float(grad_scale), pred.data_ptr(), loss.data_ptr(),
         B.ptr(grad_user), B.ptr(grad_item), B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_mse_fwd_bwd")
-    if own:
-        B.raise_if_out_of_range(err, "dr_mse_fwd_bwd")
+    _done(rc, "dr_mse_fwd_bwd", own)
     return pred, loss
 
 
@@ -678,24 +683,18 @@ def mmr_rerank(
     Widths other than 64 / 128 are zero-padded per call (no cache, so every
     write to the table is seen; pass a pre-padded table to avoid the copy)."""
     dev = B.require_device(cand_items, cand_scores, item_table)
-    _need(cand_items.dtype == torch.int32 and cand_scores.dtype == torch.float32,
-          "int32 candidate ids, fp32 scores")
-    _need(cand_items.dim() == 2 and cand_items.shape == cand_scores.shape, "[n, C] inputs")
-    _need(item_table.dtype == torch.bfloat16 and item_table.dim() == 2, "item_table must be bf16 2-D")
-    item_table = pad_columns(item_table.contiguous(),
-                             _width_of(MMR_WIDTHS, item_table.size(1), "mmr_rerank"))
-    n, C = cand_items.shape
+    cand_items, cand_scores, n, C = _candidates(cand_items, cand_scores)
+    item_table = _bf16_rows(item_table, MMR_WIDTHS, "mmr_rerank")
     out = torch.empty((n, int(k_out)), dtype=torch.int32, device=dev)
     if n == 0:
         return out
-    err = B.error_counter(dev) if check else None
+    err, own = _counter(dev, check=check)
     rc = B.lib().dr_mmr_rerank(
-        cand_items.contiguous().data_ptr(), cand_scores.contiguous().data_ptr(), n, C,
-        item_table.contiguous().data_ptr(), item_table.size(0), item_table.size(1), int(k_out),
+        cand_items.data_ptr(), cand_scores.data_ptr(), n, C,
+        item_table.data_ptr(), item_table.size(0), item_table.size(1), int(k_out),
         float(lam), out.data_ptr(), B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_mmr_rerank")
-    B.raise_if_out_of_range(err, "dr_mmr_rerank")
+    _done(rc, "dr_mmr_rerank", own)
     return out
 
 
@@ -716,25 +715,19 @@ def dpp_rerank(
     candidates are silently never picked. Widths other than 64 / 128 are
     zero-padded per call, as for ``mmr_rerank``."""
     dev = B.require_device(cand_items, cand_scores, item_table)
-    _need(cand_items.dtype == torch.int32 and cand_scores.dtype == torch.float32,
-          "int32 candidate ids, fp32 scores")
-    _need(cand_items.dim() == 2 and cand_items.shape == cand_scores.shape, "[n, C] inputs")
-    _need(item_table.dtype == torch.bfloat16 and item_table.dim() == 2, "item_table must be bf16 2-D")
-    item_table = pad_columns(item_table.contiguous(),
-                             _width_of(DPP_WIDTHS, item_table.size(1), "dpp_rerank"))
-    n, C = cand_items.shape
+    cand_items, cand_scores, n, C = _candidates(cand_items, cand_scores)
+    item_table = _bf16_rows(item_table, DPP_WIDTHS, "dpp_rerank")
     out = torch.empty((n, int(k_out)), dtype=torch.int32, device=dev)
     resid = torch.empty((n, int(k_out)), dtype=torch.float32, device=dev)
     if n == 0:
         return out, resid
-    err = B.error_counter(dev) if check else None
+    err, own = _counter(dev, check=check)
     rc = B.lib().dr_dpp_rerank(
-        cand_items.contiguous().data_ptr(), cand_scores.contiguous().data_ptr(), n, C,
+        cand_items.data_ptr(), cand_scores.data_ptr(), n, C,
         item_table.data_ptr(), item_table.size(0), item_table.size(1), int(k_out),
         float(lam), out.data_ptr(), resid.data_ptr(), B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_dpp_rerank")
-    B.raise_if_out_of_range(err, "dr_dpp_rerank")
+    _done(rc, "dr_dpp_rerank", own)
     return out, resid
 
 
@@ -784,23 +777,19 @@ def calibrated_rerank(
     candidate whose label is outside [0, G) raises IndexError after the call
     (one counter read); without it such candidates are silently never picked."""
     dev = B.require_device(cand_items, cand_scores, item_labels, profile)
-    _need(cand_items.dtype == torch.int32 and cand_scores.dtype == torch.float32,
-          "int32 candidate ids, fp32 scores")
-    _need(cand_items.dim() == 2 and cand_items.shape == cand_scores.shape, "[n, C] inputs")
-    n, C = cand_items.shape
+    cand_items, cand_scores, n, C = _candidates(cand_items, cand_scores)
     labels, profile = _labels32(item_labels), _profile(profile, n)
     out = torch.empty((n, int(k_out)), dtype=torch.int32, device=dev)
     kl = torch.empty((n, int(k_out)), dtype=torch.float32, device=dev)
     if n == 0:
         return out, kl
-    err = B.error_counter(dev) if check else None
+    err, own = _counter(dev, check=check)
     rc = B.lib().dr_calibrated_rerank(
-        cand_items.contiguous().data_ptr(), cand_scores.contiguous().data_ptr(), n, C,
+        cand_items.data_ptr(), cand_scores.data_ptr(), n, C,
         labels.data_ptr(), labels.numel(), profile.size(1), profile.data_ptr(), int(k_out),
         float(lam), out.data_ptr(), kl.data_ptr(), B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_calibrated_rerank")
-    B.raise_if_out_of_range(err, "dr_calibrated_rerank")
+    _done(rc, "dr_calibrated_rerank", own)
     return out, kl
 
 
@@ -820,13 +809,12 @@ def label_profile(rowptr: torch.Tensor, items: torch.Tensor, item_labels: torch.
     out = torch.empty((n, G), dtype=torch.float32, device=dev)
     if n == 0:
         return out
-    err = B.error_counter(dev) if check else None
+    err, own = _counter(dev, check=check)
     rc = B.lib().dr_label_profile(
         rowptr.contiguous().data_ptr(), items.contiguous().data_ptr() if items.numel() else None,
         n, labels.data_ptr(), labels.numel(), G, out.data_ptr(), B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_label_profile")
-    B.raise_if_out_of_range(err, "dr_label_profile")
+    _done(rc, "dr_label_profile", own)
     return out
 
 
@@ -844,13 +832,12 @@ def calibration_kl(recs: torch.Tensor, item_labels: torch.Tensor, profile: torch
     out = torch.empty(n, dtype=torch.float32, device=dev)
     if n == 0:
         return out
-    err = B.error_counter(dev) if check else None
+    err, own = _counter(dev, check=check)
     rc = B.lib().dr_calibration_kl(
         recs.data_ptr() if k else None, rc_dt, n, k, labels.data_ptr(), labels.numel(),
         profile.size(1), profile.data_ptr(), out.data_ptr(), B.ptr(err), B.stream(dev),
     )
-    B.check(rc, "dr_calibration_kl")
-    B.raise_if_out_of_range(err, "dr_calibration_kl")
+    _done(rc, "dr_calibration_kl", own)
     return out
 
 

@@ -57,6 +57,53 @@ def _to(t, device):
     return t.to(device, non_blocking=True) if isinstance(t, torch.Tensor) and device else t
 
 
+# --------------------------------------------------------------------------- shared steps
+def _epoch_counter(epoch_err: Optional[torch.Tensor], device) -> torch.Tensor:
+    """The epoch's id range counter: made on the first fused batch, read once
+    after the epoch (``_backend.raise_if_out_of_range``)."""
+    return _backend.error_counter(device) if epoch_err is None else epoch_err
+
+
+def _device_ids_in_range(uid, n_users: int, item_ids, n_items: int) -> None:
+    """Range check of a DEVICE batch (``item_ids``: the batch's item id
+    tensors): one min/max reduction read back (one sync) BEFORE the kernel, so
+    a bad batch raises IndexError with the weights, the optimizer state and
+    the gradient tables as they were (the reference's nn.Embedding fails
+    before any backward; the lazy path's all-zero gradient invariant holds)."""
+    if not uid.numel():
+        return
+    lo, hi = item_ids[0].min(), item_ids[0].max()
+    for t in item_ids[1:]:
+        lo, hi = torch.minimum(lo, t.min()), torch.maximum(hi, t.max())
+    mm = torch.stack([uid.min(), uid.max(), lo, hi]).cpu().tolist()
+    if mm[0] < 0 or mm[1] >= n_users:
+        raise IndexError("index out of range in self (user_id)")
+    if mm[2] < 0 or mm[3] >= n_items:
+        raise IndexError("index out of range in self (item_id)")
+
+
+def _dense_grads(*params) -> None:
+    """The dense gradient tables the fused kernels add into."""
+    for p in params:
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+
+
+def _optimizer_step(optimizer, adam: bool, lazy: bool, rows) -> None:
+    """The step after a fused batch: for a SparseAdam (``lazy``) dr_adam_rows
+    over ``rows()``, parameter -> the unique rows the batch touched (computed
+    only here; the kernel zeroes those gradient rows); for a plain Adam
+    (``adam``) dr_adam_dense; ``optimizer.step()`` otherwise."""
+    if lazy:
+        lazy_adam_step(optimizer, rows())
+        return
+    if adam:
+        fused_adam_step(optimizer)
+    else:
+        optimizer.step()
+    optimizer.zero_grad()
+
+
 # --------------------------------------------------------------------------- scoring
 def _mse_pairs(model: MatrixFactorization, user_id, item_id, true_rel):
     """The MSE fast paths' batch on the model's device: (uid, iid, target).
@@ -91,8 +138,7 @@ def point_wise_score_loop(dataset: PointWiseDataset, model: RankingModel,
         for user_id, item_id, uf, itf, true_rel in dataset.loader(**loader_params):
             if fast and _fp32_targets(true_rel):
                 uid, iid, target = _mse_pairs(model, user_id, item_id, true_rel)
-                if epoch_err is None:
-                    epoch_err = _backend.error_counter(uid.device)
+                epoch_err = _epoch_counter(epoch_err, uid.device)
                 _, sq = ops.mse_fwd_bwd(model.user_embeddings.weight.data,
                                         model.item_embeddings.weight.data, uid, iid, target, 0.0,
                                         None, None, err=epoch_err, check=False)
@@ -282,34 +328,16 @@ def point_wise_train_loop(dataset: PointWiseDataset, model: RankingModel, loss: 
             U, I = model.user_embeddings.weight, model.item_embeddings.weight
             host = user_id.device.type == "cpu" and item_id.device.type == "cpu"
             uid, iid, target = _mse_pairs(model, user_id, item_id, true_rel)
-            if not host and uid.numel():
-                # device batches: one min/max reduction read back (one sync)
-                # BEFORE the kernel, so a bad batch raises IndexError with the
-                # weights, the optimizer state and the gradient tables as they
-                # were (as in pair_wise_train_loop)
-                mm = torch.stack([uid.min(), uid.max(), iid.min(), iid.max()]).cpu().tolist()
-                if mm[0] < 0 or mm[1] >= U.size(0):
-                    raise IndexError("index out of range in self (user_id)")
-                if mm[2] < 0 or mm[3] >= I.size(0):
-                    raise IndexError("index out of range in self (item_id)")
-            if U.grad is None:
-                U.grad = torch.zeros_like(U)
-            if I.grad is None:
-                I.grad = torch.zeros_like(I)
-            if epoch_err is None:
-                epoch_err = _backend.error_counter(uid.device)
+            if not host:
+                _device_ids_in_range(uid, U.size(0), (iid,), I.size(0))
+            _dense_grads(U, I)
+            epoch_err = _epoch_counter(epoch_err, uid.device)
             B = uid.numel()
             grad_scale = 1.0 / B if loss.reduction == "mean" else 1.0
             _, sq = ops.mse_fwd_bwd(U.data, I.data, uid, iid, target, grad_scale, U.grad, I.grad,
                                     err=epoch_err, check=False)
-            if lazy:  # touched rows only; the kernel zeroes those gradient rows
-                lazy_adam_step(optimizer, {U: torch.unique(uid), I: torch.unique(iid)})
-            elif adam:
-                fused_adam_step(optimizer)
-                optimizer.zero_grad()
-            else:
-                optimizer.step()
-                optimizer.zero_grad()
+            _optimizer_step(optimizer, adam, lazy,
+                            lambda: {U: torch.unique(uid), I: torch.unique(iid)})
             batch_losses.append(loss.reduce_loss_values(sq))
             if n_scores:  # MSELoss.point_wise = the squared errors, reduced as each score says
                 batch_scores.append(torch.stack([s.reduce_loss_values(sq) for s in scores]))
@@ -435,24 +463,10 @@ def _bpr_fused_batch(model: MatrixFactorization, user_id, pos, neg, epoch_err):
         _backend.host_ids_in_range(pos, I.size(0), "positive item_id")
         _backend.host_ids_in_range(neg, I.size(0), "negative item_id")
     uid, pid, nid = (t.to(dev, torch.int64, non_blocking=True) for t in (user_id, pos, neg))
-    if not host and uid.numel():
-        # device batches: one min/max reduction read back (one sync)
-        # BEFORE the kernel, so a bad batch raises IndexError with the
-        # weights, the optimizer state and the gradient tables as they
-        # were (the reference's nn.Embedding fails before any backward;
-        # the lazy path's all-zero gradient invariant holds)
-        mm = torch.stack([uid.min(), uid.max(), torch.minimum(pid.min(), nid.min()),
-                          torch.maximum(pid.max(), nid.max())]).cpu().tolist()
-        if mm[0] < 0 or mm[1] >= U.size(0):
-            raise IndexError("index out of range in self (user_id)")
-        if mm[2] < 0 or mm[3] >= I.size(0):
-            raise IndexError("index out of range in self (item_id)")
-    if U.grad is None:
-        U.grad = torch.zeros_like(U)
-    if I.grad is None:
-        I.grad = torch.zeros_like(I)
-    if epoch_err is None:
-        epoch_err = _backend.error_counter(dev)
+    if not host:
+        _device_ids_in_range(uid, U.size(0), (pid, nid), I.size(0))
+    _dense_grads(U, I)
+    epoch_err = _epoch_counter(epoch_err, dev)
     B = uid.numel()
     losses_b, hits = ops.bpr_fwd_bwd(U.data, I.data, uid, pid, nid, 1.0 / B, U.grad, I.grad,
                                      err=epoch_err, check=False)
@@ -479,15 +493,8 @@ def pair_wise_train_loop(dataset: PairWiseDataset, model: RankingModel, loss: Pa
                                                                         epoch_err)
             B = uid.numel()
             loss_value = torch.sum(losses_b, dim=0) / B
-            if lazy:  # touched rows only; the kernel zeroes those gradient rows
-                lazy_adam_step(optimizer, {U: torch.unique(uid),
-                                           I: torch.unique(torch.cat([pid, nid]))})
-            elif adam:
-                fused_adam_step(optimizer)
-                optimizer.zero_grad()
-            else:
-                optimizer.step()
-                optimizer.zero_grad()
+            _optimizer_step(optimizer, adam, lazy, lambda: {
+                U: torch.unique(uid), I: torch.unique(torch.cat([pid, nid]))})
             batch_losses.append(loss_value.detach())
             if n_scores:  # AUCScore.pair_wise = the hit flags, reduced as each score says
                 batch_scores.append(torch.stack(
@@ -592,22 +599,14 @@ def diversity_pair_wise_train_loop(dataset: PairWiseDataset, model: MatrixFactor
         with torch.no_grad():
             items, _ = model.score_topk(k, user_ids=users)
             batch_ilds.append(diversity.per_user(items).mean())
-        if I.grad is None:
-            I.grad = torch.zeros_like(I)
-        if epoch_err is None:
-            epoch_err = _backend.error_counter(dev)
+        _dense_grads(I)
+        epoch_err = _epoch_counter(epoch_err, dev)
         ops.ild_embedding_backward(items, I.data, D.kind, I.grad,
                                    scale=-float(diversity_weight) / users.numel(),
                                    err=epoch_err, check=False)
-        if lazy:  # the lists' items are touched rows too: their gradient rows are zeroed
-            lazy_adam_step(optimizer, {U: users,
-                                       I: torch.unique(torch.cat([pid, nid, items.reshape(-1)]))})
-        elif adam:
-            fused_adam_step(optimizer)
-            optimizer.zero_grad()
-        else:
-            optimizer.step()
-            optimizer.zero_grad()
+        # the lists' items are touched rows too: their gradient rows are zeroed
+        _optimizer_step(optimizer, adam, lazy, lambda: {
+            U: users, I: torch.unique(torch.cat([pid, nid, items.reshape(-1)]))})
     _backend.raise_if_out_of_range(epoch_err, "diversity_pair_wise_train_loop")
     mean_loss, means = _pair_wise_epoch_means(batch_losses, batch_scores, n_scores)
     ilds = torch.stack(batch_ilds).double().cpu().tolist()

@@ -1246,6 +1246,26 @@ def test_mmr_rerank_persistent_prefetch_short_lists(d, C):
     assert all(sorted(got[u].tolist()) == sorted(cand[u].tolist()) for u in users)
 
 
+def test_mmr_rerank_under_the_scan_slots_cap():
+    """The grid cap of the re-rankers (dr::persistent_cus) on the MMR path: 7
+    users under scan_slots = 2 are 3 or 4 users per workgroup, all but the
+    first prefetched by LDS-DMA. One user has empty (-1) slots in tile 0. The
+    lists equal those of the uncapped grid element for element, and replay as
+    valid greedy steps (float64)."""
+    rng = np.random.default_rng(64 + 40 + 8)
+    d, ni, n, C, kout, lam = 64, 2000, 7, 40, 8, 0.5
+    E = oracle.as_bf16_f32((rng.standard_normal((ni, d)) / np.sqrt(d)).astype(np.float32))
+    cand = np.stack([rng.choice(ni, C, replace=False) for _ in range(n)]).astype(np.int32)
+    sc = -np.sort(-rng.random((n, C)), axis=1).astype(np.float32)
+    cand[4, [0, 3, 17]] = -1  # a prefetched user (workgroup 0's third)
+    args = (torch.from_numpy(cand).to(DEV), torch.from_numpy(sc).to(DEV), _bf16(E), kout, lam)
+    free = ops.mmr_rerank(*args).cpu().numpy()
+    with _backend.plan_knobs(scan_slots=2):
+        capped = ops.mmr_rerank(*args).cpu().numpy()
+    assert np.array_equal(capped, free)
+    assert _mmr_check_positions(capped, cand, sc, E, lam, tol=1e-4) == 0
+
+
 def test_padded_item_table_sees_data_writes():
     """ILD / MMR on a width without a kernel instance (d = 100) pad the item
     table per call, with no cache: writes through ``.data`` (which

@@ -24,7 +24,6 @@ profiles/calibration/ were written this way).
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,25 +32,12 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from divrec import _backend, models, ops  # noqa: E402
+from _timing import timed  # noqa: E402  (tools/_timing.py)
 
 HBM_TBS = 8.0                       # MI355X vendor peak
 ALPHA = float(np.float32(0.01))     # DR_CALIB_ALPHA
 ONE_M = float(np.float32(1) - np.float32(0.01))
 FLT_MAX = float(np.finfo(np.float32).max)
-
-
-def event_ms(fn, dev):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize(dev)
-    return e0.elapsed_time(e1)
-
-
-def timed(fn, dev, reps, warmup):
-    ms = [event_ms(fn, dev) for _ in range(warmup + reps)][warmup:]
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms)}
 
 
 def _tree_sum(x):

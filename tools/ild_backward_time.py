@@ -21,7 +21,6 @@ kernel's ms per call (HIP events, median / min / max over ``--reps`` after
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,23 +28,10 @@ sys.path.insert(0, os.path.join(ROOT, "diversity-recommendations_amd"))
 import torch  # noqa: E402
 
 from divrec import _backend, models, ops  # noqa: E402
+from _timing import timed  # noqa: E402  (tools/_timing.py)
 
 ATOMIC_TBS = 1.3  # chip-wide fp32 atomic add rate, contiguous 128-B segments
 KINDS = ("cosine", "dot", "euclidean")
-
-
-def event_ms(fn, dev):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize(dev)
-    return e0.elapsed_time(e1)
-
-
-def timed(fn, dev, reps, warmup):
-    ms = [event_ms(fn, dev) for _ in range(warmup + reps)][warmup:]
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms)}
 
 
 def torch_ild_sum(E, kind):
