@@ -86,6 +86,7 @@ SIGNATURES = {
     "dr_calibration_kl": (_i32, [_p, _i32, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _p]),
     "dr_rank_metrics": (_i32, [_p, _i32, _i64, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "dr_catalog_histogram": (_i32, [_p, _i32, _i64, _i32, _i64, _p, _p, _p]),
+    "dr_als_solve": (_i32, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _f32, _f32, _p, _p, _p]),
 }
 
 _LIB: Optional[ctypes.CDLL] = None

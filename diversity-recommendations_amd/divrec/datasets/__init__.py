@@ -7,6 +7,7 @@ from .base_datasets import (
     PointWiseRow,
     RankingDataset,
     RankingRow,
+    interaction_csr,
 )
 from .storages import Features, UserItemInteractionsDataset
 
@@ -21,4 +22,5 @@ __all__ = [
     "PointWiseDataset",
     "RankingDataset",
     "RankingRow",
+    "interaction_csr",
 ]

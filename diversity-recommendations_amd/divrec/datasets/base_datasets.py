@@ -138,6 +138,55 @@ def _device_csr(data: UserItemInteractionsDataset, n_users: int, n_items: int, d
     return rowptr, items.to(torch.int32).contiguous()
 
 
+def interaction_csr(data: UserItemInteractionsDataset, n_users: int, n_items: int, device,
+                    by: str = "user", use_scores: bool = False):
+    """The interactions of ``data`` as the CSR ``ops.als_solve`` takes, on
+    ``device`` (torch ops only, so ``"cpu"`` works): (rowptr int64 [rows + 1],
+    cols int32, values fp32 or None) over the unique (user, item) pairs, the
+    columns sorted per row. ``by="user"``: one row per user over item columns;
+    ``by="item"``: the transpose. With ``use_scores`` the values are
+    ``interaction_scores[row of the interaction]`` summed over the repeats of a
+    pair (float64 sums in interaction order, rounded once); without it None
+    (every pair counts 1). ``n_users`` / ``n_items`` may exceed the data's own
+    counts (rows without entries); ValueError if they are below them."""
+    if by not in ("user", "item"):
+        raise ValueError(f'by must be "user" or "item", got {by!r}')
+    n_users, n_items = int(n_users), int(n_items)
+    if n_users < int(data.number_of_users) or n_items < int(data.number_of_items):
+        raise ValueError(f"the data has {int(data.number_of_users)} users and "
+                         f"{int(data.number_of_items)} items: more than n_users = {n_users}, "
+                         f"n_items = {n_items}")
+    n_rows, span = (n_users, n_items) if by == "user" else (n_items, n_users)
+    values = None
+    if data.interactions is None or data.interactions.numel() == 0:
+        key = torch.zeros(0, dtype=torch.int64, device=device)
+        if use_scores:
+            values = torch.zeros(0, dtype=torch.float32, device=device)
+    else:
+        inter = data.interactions.to(device=device, dtype=torch.int64)
+        r, c = (inter[:, 0], inter[:, 1]) if by == "user" else (inter[:, 1], inter[:, 0])
+        key = r * span + c
+        if use_scores:
+            # stable sort, then each pair's sum as a difference of one running
+            # float64 sum: no atomics, the same values on every run
+            key, order = torch.sort(key, stable=True)
+            run = torch.cumsum(data.interaction_scores.to(device=device, dtype=torch.float64)[order], 0)
+            last = torch.ones_like(key, dtype=torch.bool)
+            last[:-1] = key[1:] != key[:-1]
+            ends = run[last]
+            values = ends.clone()
+            values[1:] -= ends[:-1]
+            values = values.to(torch.float32)
+            key = key[last]
+        else:
+            key = torch.unique(key)  # sorted, unique
+    rows, cols = key // span, key % span
+    counts = torch.bincount(rows, minlength=n_rows)
+    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=device)
+    rowptr[1:] = torch.cumsum(counts, 0)
+    return rowptr, cols.to(torch.int32).contiguous(), values
+
+
 class DevicePointWiseDataset:
     """PointWiseDataset resident on ``device``: ``loader`` yields whole batches
     ``(user_id, item_id, None, None, true_relevance)`` as device tensors (int64

@@ -128,6 +128,34 @@ class MatrixFactorization(RankingModel):
         """bf16 copies of both tables (the fast scoring mode's operands)."""
         return self.scoring_tables("bf16")
 
+    def _user_side(self, user_vectors: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+        """``user_vectors`` (fp32 [n, embedding_dim]) as the user table of a
+        scan beside ``like``, the model's own: its dtype and padded width."""
+        if (user_vectors.dim() != 2 or user_vectors.size(1) != self.embedding_dim
+                or user_vectors.dtype != torch.float32):
+            raise ValueError(f"user_vectors must be fp32 [n, {self.embedding_dim}], got "
+                             f"{user_vectors.dtype} {tuple(user_vectors.shape)}")
+        rows = user_vectors.detach().to(like.device, like.dtype).contiguous()
+        return ops.pad_columns(rows, like.size(1))
+
+    @torch.no_grad()
+    def fold_in_users(self, rowptr: torch.Tensor, items: torch.Tensor,
+                      weights: Optional[torch.Tensor] = None, alpha: float = 40.0,
+                      reg: float = 0.1) -> torch.Tensor:
+        """Embeddings of users the model has never seen, from their histories
+        (CSR: rowptr int64 [n + 1], items int32, ``weights`` fp32 or None):
+        fp32 [n, embedding_dim], each row the ALS solve of that history against
+        the model's item table (``ops.als_solve``; ``alpha`` and ``reg`` as in
+        ``als_train_loop``). The rows go to ``score_topk`` and
+        ``recommend_diverse`` as ``user_vectors``. An item id outside the item
+        table raises IndexError."""
+        dev = self._device()
+        if self.embedding_dim > ops.ALS_WIDTHS[-1]:
+            raise ValueError(f"fold_in_users supports embedding_dim <= {ops.ALS_WIDTHS[-1]}")
+        w = None if weights is None else weights.to(dev, torch.float32)
+        return ops.als_solve(self.item_embeddings.weight.detach(), rowptr.to(dev, torch.int64),
+                             items.to(dev, torch.int32), w, alpha=alpha, reg=reg)
+
     @torch.no_grad()
     def score_topk(
         self,
@@ -136,15 +164,24 @@ class MatrixFactorization(RankingModel):
         exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
         precision: str = "fp32",
         n_items: Optional[int] = None,
+        *,
+        user_vectors: Optional[torch.Tensor] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k items of each user (all users, or ``user_ids``) over the
         catalog (the first ``n_items`` item rows; default all): (items int64
         [n, k], scores fp32 [n, k]) on the model's device, ordered by score
         desc then item id asc. ``exclude`` = (rowptr int64 [n+1], items int32)
         CSR of items never to return. ``precision`` "fp32" (default, the
-        reference's arithmetic) or "bf16" (fast mode)."""
+        reference's arithmetic) or "bf16" (fast mode). ``user_vectors`` (fp32
+        [n, embedding_dim], e.g. ``fold_in_users``): these rows are the user
+        side of the scan instead of the model's user table, converted and
+        padded like ``scoring_tables``; ``user_ids`` must then be None."""
+        if user_vectors is not None and user_ids is not None:
+            raise ValueError("user_vectors are the users to score: user_ids must be None")
         dev = self._device()
         U, I = self.scoring_tables(precision)
+        if user_vectors is not None:
+            U = self._user_side(user_vectors, U)
         if n_items is not None:
             I = I[: int(n_items)]
         uids = None if user_ids is None else _on_device(dev, user_ids)
@@ -169,6 +206,7 @@ class MatrixFactorization(RankingModel):
         item_labels: Optional[torch.Tensor] = None,
         user_profile: Optional[torch.Tensor] = None,
         n_labels: Optional[int] = None,
+        user_vectors: Optional[torch.Tensor] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Diversity re-ranked lists: the top-``candidates`` items of each user
         (``score_topk`` with the same ``user_ids`` / ``exclude`` / ``precision``
@@ -179,11 +217,16 @@ class MatrixFactorization(RankingModel):
         values in [0, G)) and ``user_profile`` (fp32 [n, G], one row per
         listed user, e.g. ``ops.label_profile`` of the users' history;
         ``n_labels``, when given, must equal G <= 64) and uses no item rows.
+        ``user_vectors`` (fp32 [n, embedding_dim], e.g. ``fold_in_users``)
+        replaces the model's users as in ``score_topk``; ``user_ids`` must
+        then be None.
         Returns (items int64 [n, k] in pick order,
         scores fp32 [n, k]: the picks' scan scores). A list that ends early
         (fewer eligible candidates than ``k``) holds item -1 / score -inf.
         ``k <= candidates <= min(1024, catalog)``, else ValueError."""
         k, candidates = int(k), int(candidates)
+        if user_vectors is not None and user_ids is not None:
+            raise ValueError("user_vectors are the users to score: user_ids must be None")
         if method not in RERANKERS:
             raise ValueError(f"method must be one of {sorted(RERANKERS)}, got {method!r}")
         catalog = self.no_items if n_items is None else int(n_items)
@@ -194,6 +237,8 @@ class MatrixFactorization(RankingModel):
             if item_labels is None or user_profile is None:
                 raise ValueError('method "calibrated" needs item_labels and user_profile')
             n_lists = self.no_users if user_ids is None else len(user_ids)
+            if user_vectors is not None:
+                n_lists = len(user_vectors)
             if user_profile.dim() != 2 or user_profile.size(0) != n_lists:
                 raise ValueError(f"user_profile must be [{n_lists}, n_labels], one row per user, "
                                  f"got {tuple(user_profile.shape)}")
@@ -208,7 +253,8 @@ class MatrixFactorization(RankingModel):
             raise ValueError(f'item_labels, user_profile and n_labels belong to method '
                              f'"calibrated", not {method!r}')
         cand, cand_scores = self.score_topk(candidates, user_ids=user_ids, exclude=exclude,
-                                            precision=precision, n_items=n_items)
+                                            precision=precision, n_items=n_items,
+                                            user_vectors=user_vectors)
         cand32 = cand.to(torch.int32)
         if method == "calibrated":
             dev = cand.device

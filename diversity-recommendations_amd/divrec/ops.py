@@ -862,3 +862,155 @@ def rank_metrics(
     )
     B.check(rc, "dr_rank_metrics")
     return tuple(outs)
+
+
+# --------------------------------------------------------------------------- ALS
+ALS_WIDTHS = (32, 64, 128)  # dr_als_solve instances; others are zero-padded
+GRAM_CHUNK_ROWS = 1 << 20   # rows of a table converted to float64 at a time
+GRAM_BLOCK_ROWS = 4096      # rows per product of the batched Gram sum
+
+
+def _gram64(table: torch.Tensor) -> torch.Tensor:
+    """table^T table in float64, [d, d], summed over row chunks."""
+    _need(table.dim() == 2 and table.dtype == torch.float32, "table must be fp32 2-D")
+    d = table.size(1)
+    g = torch.zeros((d, d), dtype=torch.float64, device=table.device)
+    for r0 in range(0, table.size(0), GRAM_CHUNK_ROWS):
+        t = table[r0:r0 + GRAM_CHUNK_ROWS].to(torch.float64)
+        # blocks of GRAM_BLOCK_ROWS rows as one batched product, then their sum:
+        # a single [d, rows] x [rows, d] product keeps few workgroups busy
+        whole = t.size(0) // GRAM_BLOCK_ROWS * GRAM_BLOCK_ROWS
+        if whole:
+            blocks = t[:whole].view(-1, GRAM_BLOCK_ROWS, d)
+            g += torch.bmm(blocks.transpose(1, 2), blocks).sum(0)
+        if whole < t.size(0):
+            g += t[whole:].T @ t[whole:]
+    return g
+
+
+def gram(table: torch.Tensor) -> torch.Tensor:
+    """G = table^T table, fp32 [d, d]: the Gram matrix ``als_solve`` takes. A
+    torch product in float64 (row chunks of at most 2^20 rows, so the float64
+    copy stays small), made exactly symmetric and rounded once to fp32. One
+    d x d product per half-step, under 1 % of the solve's work."""
+    g = _gram64(table)
+    return ((g + g.T) * 0.5).to(torch.float32)
+
+
+_gram_of = gram  # als_solve has an argument of that name
+
+
+def _csr(rowptr: torch.Tensor, cols: torch.Tensor, weights: Optional[torch.Tensor]):
+    """A CSR's (rowptr int64 [n + 1], cols int32 [nnz], weights fp32 [nnz] or
+    None), contiguous, and n. rowptr is checked against cols (one host sync):
+    the kernel reads cols[rowptr[r] : rowptr[r + 1]] as it is told."""
+    _need(rowptr.dtype == torch.int64 and rowptr.dim() == 1 and rowptr.numel() >= 1,
+          "rowptr int64 [n + 1]")
+    _need(cols.dtype == torch.int32 and cols.dim() == 1, "cols must be int32 1-D")
+    if weights is not None:
+        _need(weights.dtype == torch.float32 and weights.shape == cols.shape,
+              "weights must be fp32, one per entry of cols")
+        weights = weights.contiguous()
+    rowptr, cols = rowptr.contiguous(), cols.contiguous()
+    n = rowptr.numel() - 1
+    first, last, falls = torch.stack(
+        [rowptr[0], rowptr[-1], (rowptr[1:] < rowptr[:-1]).sum()]).tolist()
+    _need(first == 0 and last == cols.numel() and falls == 0,
+          "rowptr must rise from 0 to the number of entries of cols")
+    return rowptr, cols, weights, n
+
+
+def als_solve(
+    fixed_table: torch.Tensor, rowptr: torch.Tensor, cols: torch.Tensor,
+    weights: Optional[torch.Tensor] = None, alpha: float = 1.0, reg: float = 0.1,
+    gram: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, check: bool = True,
+) -> torch.Tensor:
+    """One implicit-feedback ALS half-step (dr_als_solve, Hu, Koren, Volinsky
+    2008): fp32 [n, d], row r the exact minimiser of
+    ``sum_i c_ri (p_ri - x^T y_i)^2 + reg |x|^2`` over the fp32 ``fixed_table``
+    [m, d], with c = 1 + alpha * w and p = 1 on the entries of row r of the CSR
+    (rowptr int64 [n + 1], cols int32, ``weights`` fp32 or None = 1) and c = 1,
+    p = 0 elsewhere: ``x = (G + alpha sum_i w_i y_i y_i^T + reg I)^-1
+    sum_i (1 + alpha w_i) y_i`` by an fp32 Cholesky. ``gram`` is G =
+    ``ops.gram(fixed_table)`` (computed here when None; pass it when solving
+    several CSRs against one table). ``out`` (fp32 [n, d], contiguous) is
+    written in place and returned. An empty row is exactly 0; a repeated column
+    counts once per occurrence; a row with a non-positive or non-finite pivot
+    (negative or non-finite weights) is all NaN. With ``check`` a cols entry
+    outside [0, m) raises IndexError after the call (one counter read);
+    without it the entry contributes nothing. Widths other than 32 / 64 / 128
+    are zero-padded per call, which is exact: the padded coordinates solve to 0.
+    Results are bitwise reproducible and independent of the grid."""
+    dev = B.require_device(fixed_table, rowptr, cols, weights, gram, out)
+    _need(fixed_table.dim() == 2 and fixed_table.dtype == torch.float32,
+          "fixed_table must be fp32 2-D")
+    _contig(fixed_table, "fixed_table")
+    m, d = fixed_table.shape
+    _need(d >= 1, "fixed_table must have columns")
+    w = _width_of(ALS_WIDTHS, d, "als_solve")
+    alpha, reg = float(alpha), float(reg)
+    _need(0.0 <= alpha < float("inf"), "alpha must be >= 0 and finite")
+    _need(0.0 < reg < float("inf"), "reg must be > 0 and finite")
+    rowptr, cols, weights, n = _csr(rowptr, cols, weights)
+    if out is not None:
+        _need(out.dtype == torch.float32 and out.shape == (n, d) and out.is_contiguous(),
+              "out must be a contiguous fp32 [n, d] tensor")
+    if gram is None:
+        gram = _gram_of(fixed_table)
+    _need(gram.dtype == torch.float32 and gram.shape == (d, d), "gram must be fp32 [d, d]")
+    if w != d:
+        fixed_table = pad_columns(fixed_table, w)
+        padded = torch.zeros((w, w), dtype=torch.float32, device=dev)
+        padded[:d, :d] = gram
+        gram = padded
+    gram = gram.contiguous()
+    res = out if out is not None and w == d else torch.empty((n, w), dtype=torch.float32, device=dev)
+    if n:
+        err, own = _counter(dev, check=check)
+        rc = B.lib().dr_als_solve(
+            fixed_table.data_ptr() if m else None, m, w, gram.data_ptr(), rowptr.data_ptr(),
+            cols.data_ptr() if cols.numel() else None, B.ptr(weights) if cols.numel() else None,
+            n, alpha, reg, res.data_ptr(), B.ptr(err), B.stream(dev),
+        )
+        _done(rc, "dr_als_solve", own)
+    if w == d:
+        return res
+    if out is None:
+        return res[:, :d].contiguous()
+    out.copy_(res[:, :d])
+    return out
+
+
+def als_objective(
+    row_table: torch.Tensor, fixed_table: torch.Tensor, rowptr: torch.Tensor, cols: torch.Tensor,
+    weights: Optional[torch.Tensor], alpha: float, reg: float,
+) -> float:
+    """The implicit-feedback objective ALS descends, as a Python float:
+    ``J = sum_r [x_r^T G x_r + sum_{i in r} (c_ri (1 - s_ri)^2 - s_ri^2)]
+    + reg (|X|^2 + |Y|^2)`` with X = ``row_table`` [n, d], Y = ``fixed_table``
+    [m, d] (both fp32), G = Y^T Y, s_ri = x_r^T y_i (``gather_dot``) and
+    c = 1 + alpha * w over the CSR's entries; every sum in float64 on the
+    device. Equal to the sum over ALL (r, i) of c (p - s)^2 plus the
+    regulariser, without visiting the unobserved pairs."""
+    B.require_device(row_table, fixed_table, rowptr, cols, weights)
+    _need(row_table.dim() == 2 and fixed_table.dim() == 2 and
+          row_table.dtype == torch.float32 and fixed_table.dtype == torch.float32 and
+          row_table.size(1) == fixed_table.size(1), "fp32 2-D tables of one width")
+    row_table, fixed_table = row_table.contiguous(), fixed_table.contiguous()
+    rowptr, cols, weights, n = _csr(rowptr, cols, weights)
+    _need(n == row_table.size(0), "one CSR row per row of row_table")
+    total = torch.zeros((), dtype=torch.float64, device=row_table.device)
+    if cols.numel():
+        rows = torch.repeat_interleave(torch.arange(n, device=cols.device), rowptr[1:] - rowptr[:-1])
+        s = gather_dot(row_table, fixed_table, rows, cols.to(torch.int64)).to(torch.float64)
+        c = 1.0 if weights is None else weights.to(torch.float64)
+        c = 1.0 + float(alpha) * c
+        total += (c * (1.0 - s) ** 2 - s * s).sum()
+    g = _gram64(fixed_table)
+    sq = torch.zeros((), dtype=torch.float64, device=row_table.device)
+    for r0 in range(0, n, GRAM_CHUNK_ROWS):
+        x = row_table[r0:r0 + GRAM_CHUNK_ROWS].to(torch.float64)
+        total += ((x @ g) * x).sum()
+        sq += (x * x).sum()
+    total += float(reg) * (sq + torch.diagonal(g).sum())
+    return float(total.item())

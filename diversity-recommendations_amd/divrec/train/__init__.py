@@ -1,4 +1,5 @@
 from .utils import (
+    als_train_loop,
     diversity_pair_wise_train_loop,
     fused_adam_step,
     get_diverse_recommendations,
@@ -20,6 +21,7 @@ __all__ = [
     "point_wise_train_loop",
     "pair_wise_train_loop",
     "diversity_pair_wise_train_loop",
+    "als_train_loop",
     "recommendations_train_loop",
     "fused_adam_step",
 ]

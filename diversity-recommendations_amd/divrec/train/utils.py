@@ -20,6 +20,8 @@ Same functions, arguments and return values as the reference. On the hot path:
 * ``diversity_pair_wise_train_loop`` (not in the reference) trains the BPR
   objective minus a weighted ILD of the model's own top-k lists: the pairwise
   part as above, the regulariser's gradient by dr_ild_embedding_backward.
+* ``als_train_loop`` (not in the reference) trains a MatrixFactorization by
+  implicit-feedback alternating least squares: two dr_als_solve per iteration.
 """
 from __future__ import annotations
 
@@ -30,7 +32,13 @@ import torch
 from torch.autograd.graph import increment_version
 
 from divrec import _backend, ops
-from divrec.datasets import PairWiseDataset, PointWiseDataset, RankingDataset
+from divrec.datasets import (
+    PairWiseDataset,
+    PointWiseDataset,
+    RankingDataset,
+    UserItemInteractionsDataset,
+    interaction_csr,
+)
 from divrec.losses import (
     EmbeddingDistance,
     IntraListDiversityScore,
@@ -611,6 +619,53 @@ def diversity_pair_wise_train_loop(dataset: PairWiseDataset, model: MatrixFactor
     mean_loss, means = _pair_wise_epoch_means(batch_losses, batch_scores, n_scores)
     ilds = torch.stack(batch_ilds).double().cpu().tolist()
     return mean_loss, means, sum(ilds) / len(ilds)
+
+
+def als_train_loop(data: UserItemInteractionsDataset, model: MatrixFactorization,
+                   iterations: int, alpha: float = 40.0, reg: float = 0.1,
+                   use_scores: bool = False, compute_loss: bool = True) -> List[float]:
+    """Implicit-feedback ALS (Hu, Koren, Volinsky 2008; not in the reference):
+    ``iterations`` times, solve every user row against the item table, then
+    every item row against the user table (``ops.als_solve``: a closed-form
+    solve per row, no sampler, no learning rate, no atomics), writing
+    ``weight.data`` of both embeddings in place. The confidence of a pair is
+    1 + alpha (or 1 + alpha * its summed ``interaction_scores`` with
+    ``use_scores``); users and items of the model beyond the data's get zero
+    rows. Returns the objective ``ops.als_objective`` before the first
+    half-step and after every half-step (1 + 2 * iterations floats, each a
+    host sync), or [] without ``compute_loss``. ValueError for a model that is
+    not a plain MatrixFactorization, for tables that do not cover ``data`` and
+    for ``embedding_dim`` > 128; RuntimeError for a model on the CPU."""
+    if not _mf_scoring(model):
+        raise ValueError("als_train_loop needs a MatrixFactorization model (its own forward)")
+    if model.embedding_dim > ops.ALS_WIDTHS[-1]:
+        raise ValueError(f"als_train_loop supports embedding_dim <= {ops.ALS_WIDTHS[-1]}, "
+                         f"got {model.embedding_dim}")
+    if int(data.number_of_users) > model.no_users or int(data.number_of_items) > model.no_items:
+        raise ValueError(f"the model's tables ({model.no_users} users, {model.no_items} items) do "
+                         f"not cover the data ({int(data.number_of_users)} users, "
+                         f"{int(data.number_of_items)} items)")
+    if int(iterations) < 0:
+        raise ValueError("iterations must be >= 0")
+    dev = model._device()
+    by_user = interaction_csr(data, model.no_users, model.no_items, dev, "user", use_scores)
+    by_item = interaction_csr(data, model.no_users, model.no_items, dev, "item", use_scores)
+    U, I = model.user_embeddings.weight, model.item_embeddings.weight
+    history: List[float] = []
+
+    def objective() -> None:
+        if compute_loss:
+            history.append(ops.als_objective(U.data, I.data, *by_user, alpha, reg))
+
+    with torch.no_grad():
+        objective()
+        for _ in range(int(iterations)):
+            for table, fixed, csr in ((U, I, by_user), (I, U, by_item)):
+                # the ids come from the data, checked against the tables above
+                ops.als_solve(fixed.data, *csr, alpha=alpha, reg=reg, out=table.data, check=False)
+                increment_version(table)  # raw-pointer update, as in fused_adam_step
+                objective()
+    return history
 
 
 def recommendations_train_loop(dataset: RankingDataset, model: RankingModel,

@@ -492,6 +492,38 @@ int dr_calibration_kl(const void* recs, int rec_dtype, int64_t n_users, int k,
                       const int32_t* item_labels, int64_t n_items, int G, const float* profile,
                       float* out, int32_t* err, dr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Implicit-feedback ALS row solve (Hu, Koren, Volinsky, ICDM 2008; no
+ * reference symbol): one half-step of alternating least squares, and the
+ * fold-in of rows the model has never seen. fixed_table Y fp32 [n_fixed_rows,
+ * d] stays fixed; the rows to solve are a CSR over it (rowptr int64
+ * [n_rows + 1], cols int32 [nnz], weights fp32 [nnz] or NULL = all 1). For
+ * row r with entries (i, w_i):
+ *   A_r = G + alpha * sum_i w_i y_i y_i^T + reg * I     G = Y^T Y, fp32 [d, d]
+ *   b_r = sum_i (1 + alpha * w_i) y_i
+ *   x_r = A_r^-1 b_r                                    (Cholesky, fp32)
+ * the exact minimiser over x_r of sum_i c_ri (p_ri - x_r^T y_i)^2 + reg |x_r|^2
+ * with c = 1 + alpha w, p = 1 on the row's entries and c = 1, p = 0 elsewhere.
+ * gram is an argument (one d x d product per half-step, the caller's) and
+ * must be symmetric. out fp32 [n_rows, d].
+ * An empty row gives x_r = 0 exactly. A cols entry outside [0, n_fixed_rows)
+ * contributes nothing and is added to *err (a 32-bit device counter, may be
+ * NULL). A repeated column contributes once per occurrence. A row whose
+ * Cholesky meets a pivot that is not finite or <= 0 (negative or non-finite
+ * weights only) is a whole row of NaN. No atomics touch the result: a row
+ * depends on its own entries only, bitwise, whatever the grid or its place in
+ * the CSR. rowptr must be non-decreasing with rowptr[n_rows] = nnz (the
+ * caller's to check; the kernel reads cols[rowptr[r] .. rowptr[r + 1])).
+ * d in {32, 64, 128}, alpha >= 0, reg > 0 (all finite), n_fixed_rows in
+ * [0, 2^31); cols may be NULL when every row is empty, fixed_table when
+ * n_fixed_rows = 0. n_rows = 0 is a no-op.
+ * Launch: one 256-thread workgroup per row at a time, a persistent grid of as
+ * many workgroups per CU as are resident (DR_KNOB_SCAN_SLOTS caps the CUs, as
+ * for dr_dpp_rerank). */
+int dr_als_solve(const float* fixed_table, int64_t n_fixed_rows, int d, const float* gram,
+                 const int64_t* rowptr, const int32_t* cols, const float* weights, int64_t n_rows,
+                 float alpha, float reg, float* out, uint32_t* err, dr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
