@@ -514,17 +514,22 @@ def bpr_fwd_bwd(
     checked by the caller (pair_wise_train_loop: once per epoch)."""
     dev = B.require_device(user_table, item_table, user_id, pos_id, neg_id, grad_user, grad_item)
     _need(user_table.dtype == torch.float32 and item_table.dtype == torch.float32, "fp32 tables")
+    _need(user_table.dim() == 2 and item_table.dim() == 2, "tables must be 2-D")
+    _need(user_table.size(1) == item_table.size(1), "tables must share embedding_dim")
+    _contig(user_table, "user_table"), _contig(item_table, "item_table")
     for t in (user_id, pos_id, neg_id):
         _need(t.dtype == torch.int64 and t.dim() == 1 and t.numel() == user_id.numel(),
               "ids must be 1-D int64 of equal length")
     n = user_id.numel()
+    _grad_like(grad_user, user_table, "grad_user"), _grad_like(grad_item, item_table, "grad_item")
+    user_id, pos_id, neg_id = user_id.contiguous(), pos_id.contiguous(), neg_id.contiguous()
     loss = torch.empty(n, dtype=torch.float32, device=dev)
     hit = torch.empty(n, dtype=torch.int32, device=dev)
     err, own = _counter(dev, err, check)
     rc = B.lib().dr_bpr_fwd_bwd(
         user_table.data_ptr(), user_table.size(0), item_table.data_ptr(), item_table.size(0),
-        user_table.size(1), user_id.contiguous().data_ptr(), pos_id.contiguous().data_ptr(),
-        neg_id.contiguous().data_ptr(), n, float(grad_scale), loss.data_ptr(), hit.data_ptr(),
+        user_table.size(1), user_id.data_ptr(), pos_id.data_ptr(),
+        neg_id.data_ptr(), n, float(grad_scale), loss.data_ptr(), hit.data_ptr(),
         B.ptr(grad_user), B.ptr(grad_item), B.ptr(err), B.stream(dev),
     )
     _done(rc, "dr_bpr_fwd_bwd", own)
