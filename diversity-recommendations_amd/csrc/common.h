@@ -260,6 +260,39 @@ __device__ __forceinline__ float wave_sum_dpp_f32(float v) {  // uniform: the wa
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
+// ---------------------------------------------------------------- LDS-DMA
+// global_load_lds_*: a wave's 64 dwords (or 16-B chunks) go from global memory
+// straight into LDS, lane l's at M0 + l * 4 (or 16), with no VGPR in between;
+// the load counts in vmcnt like any other. lds_base is the wave-uniform LDS
+// byte address for M0: the caller makes it uniform (readfirstlane) where it
+// computes it. The s_nop 0 separates the M0 write from the DMA that reads it.
+
+// LDS byte address of a __shared__ object
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+  return (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)p);
+}
+
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+// one dword / one 16-B chunk per lane from the lane's own 64-bit address
+__device__ __forceinline__ void lds_dma_b32(const void* src, uint32_t lds_base) {
+  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off"
+               : : "v"(src), "s"(lds_base) : "memory", "m0");
+}
+__device__ __forceinline__ void lds_dma_b128(const void* src, uint32_t lds_base) {
+  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
+               : : "v"(src), "s"(lds_base) : "memory", "m0");
+}
+// one 16-B chunk per lane from a wave-uniform base (an SGPR pair) plus the
+// lane's 32-bit byte offset
+__device__ __forceinline__ void lds_dma_b128(const char* base, uint32_t off, uint32_t lds_base) {
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
+               :
+               : "v"(off), "s"(base), "s"(lds_base)
+               : "memory", "m0");
+}
+#pragma clang diagnostic pop
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace dr

@@ -614,7 +614,7 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
   const int ndw = k * (int)sizeof(R) / 4;  // id dwords per user
   const uint32_t buf_bytes = (uint32_t)ni * 1024u, ids_bytes = (uint32_t)nid * 256u;
   const uint32_t wave_off = kStreamHead + (uint32_t)wave * sh.wave_bytes(nb);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
+  const uint32_t lds0 = dr::lds_addr(smem);
   float* w = reinterpret_cast<float*>(smem) + wave * 128;  // per-row terms of the current user
   int* badf = reinterpret_cast<int*>(smem + kStreamWaves * 512) + wave * kStreamMaxBufs;
   const char* Eb = reinterpret_cast<const char*>(E);
@@ -625,8 +625,6 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
   auto ids_off = [&](int m) -> uint32_t {
     return wave_off + (uint32_t)nb * buf_bytes + (uint32_t)(m % (nb + 1)) * ids_bytes;
   };
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
   // the list of user m: nid dword DMAs (entries past the list repeat its last dword)
   auto issue_ids = [&](int m) {
     const char* src = reinterpret_cast<const char*>(recs + user_of(m) * k);
@@ -634,8 +632,7 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
     for (int j = 0; j < nid; ++j) {
       const int e = 64 * j + lane < ndw ? 64 * j + lane : ndw - 1;
       const uint32_t m0 = __builtin_amdgcn_readfirstlane(dst + 256u * (uint32_t)j);
-      asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off"
-                   : : "v"(src + 4 * e), "s"(m0) : "memory", "m0");
+      dr::lds_dma_b32(src + 4 * e, m0);
     }
   };
   // The rows of user m (its list landed): piece j, lane l fills image row
@@ -667,8 +664,7 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
         const int lc = (lane % CPR) ^ SW::swz(j * RPI + gq);
         const char* src = Eb + id * (uint64_t)(2 * D) + lc * 16;
         const uint32_t m0 = __builtin_amdgcn_readfirstlane(dst + 1024u * (uint32_t)j);
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                     : : "v"(src), "s"(m0) : "memory", "m0");
+        dr::lds_dma_b128(src, m0);
       }
     }
   };
@@ -826,7 +822,6 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
   if (lane == 0 && gw < 8192)
     for (int i = 0; i < 8; ++i) g_ild_diag[gw][i] = dg[i];
 #endif
-#pragma clang diagnostic pop
   // no LDS-DMA may be outstanding when the wave ends
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (nbad && err && lane == 0) atomicAdd(err, nbad);

@@ -318,13 +318,7 @@ __device__ __forceinline__ void issue_stage(const char* __restrict__ I, int64_t 
       off = (uint32_t)(rr * (2 * D) + lc * 16);
     }
     const uint32_t m0 = __builtin_amdgcn_readfirstlane(lds_stage + wave_first * 16);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :
-                 : "v"(off), "s"(base), "s"(m0)
-                 : "memory", "m0");
-#pragma clang diagnostic pop
+    dr::lds_dma_b128(base, off, m0);
   }
 }
 
@@ -842,7 +836,7 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
   // the tile is named relative to the stage's first tile (stage_t0; SR <= 255
   // tiles): no bound on the catalog length
   uint2* blk_meta = reinterpret_cast<uint2*>(blk_val + SB * 16);
-  const uint32_t lds_ring = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
+  const uint32_t lds_ring = dr::lds_addr(smem);
   // This lane's A-fragment byte offset for k-step s in a tile is
   // col*2D + ((2s + h) ^ swz(col)) * 16 = a_row + ((2s) ^ a_sw) * 16: two VALU
   // per read instead of KS resident offsets (registers are the budget here).

@@ -1089,9 +1089,14 @@ def test_mmr_rerank_invalid_candidates():
     for u in range(n):  # 0, 35, 70, ... invalid entries: fewer live than kout for most users
         cand[u, rng.choice(C, 35 * u, replace=False)] = -1
     sc = rng.standard_normal((n, C)).astype(np.float32)
+    # one more user with no live candidate at all: no first pick, and the
+    # rounds of its only batch find nothing
+    cand = np.concatenate([cand, np.full((1, C), -1, np.int32)])
+    sc = np.concatenate([sc, rng.standard_normal((1, C)).astype(np.float32)])
     got = ops.mmr_rerank(torch.from_numpy(cand).to(DEV), torch.from_numpy(sc).to(DEV), _bf16(E),
                          kout, 0.6).cpu().numpy()
-    assert _mmr_check_positions(got, cand, sc, E, 0.6, tol=1e-4) == 0
+    assert (got[n] == -1).all()
+    assert _mmr_check_positions(got[:n], cand[:n], sc[:n], E, 0.6, tol=1e-4) == 0
     for u in range(n):
         n_live = int((cand[u] >= 0).sum())
         assert (got[u, :min(n_live, kout)] >= 0).all()
