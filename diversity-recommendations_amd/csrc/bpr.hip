@@ -6,23 +6,18 @@
 //
 // bpr_fwd_bwd is HBM/atomic-bound: per triple it reads three fp32 rows
 // (3*d*4 B), 24 B of ids, writes loss/hit, and adds 3*d*4 B of gradient with
-// fp32 atomics. A group of 32 lanes owns one triple and lane l handles row
-// elements l, l+32, l+64, ...: every load and every atomic wave-instruction
-// then covers two contiguous 128-B row segments, the shape at which
-// global_atomic_add_f32 runs at its full rate (MI355X_MICROARCH.md, Global
-// float atomics); 16-B-per-lane chunks would scatter each atomic instruction
-// over 16-B strides. Any d <= 512. Out-of-range ids are range-checked
-// (include/divrec_hip.h): such a triple reads and adds nothing.
-#include <algorithm>
+// fp32 atomics, in the row-run layout of row_runs.h. Any d <= 512.
+// Out-of-range ids are range-checked (include/divrec_hip.h): such a triple
+// reads and adds nothing.
 #include <cmath>
 
-#include "common.h"
+#include "row_runs.h"
 
 namespace {
 
-constexpr int kBlock = 256;
+using dr::in_rows;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+constexpr int kBlock = 256;
 
 // -logsigmoid(x) in torch's stable form: max(-x, 0) + log1p(exp(-|x|)).
 __device__ __forceinline__ float neg_log_sigmoid(float x) {
@@ -35,8 +30,6 @@ __device__ __forceinline__ float neg_log_sigmoid_grad(float x) {
   return -(x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e));
 }
 
-__device__ __forceinline__ bool in_rows(int64_t r, int64_t n) { return r >= 0 && r < n; }
-
 template <int E>  // row elements per lane: ceil(d / 32)
 __global__ __launch_bounds__(kBlock) void bpr_kernel(
     const float* __restrict__ U, int64_t nu, const float* __restrict__ I, int64_t ni, int64_t d,
@@ -44,14 +37,11 @@ __global__ __launch_bounds__(kBlock) void bpr_kernel(
     const int64_t* __restrict__ nid, int64_t batch, int64_t span, float grad_scale,
     float* __restrict__ loss, int32_t* __restrict__ hit, float* __restrict__ gU,
     float* __restrict__ gI, int32_t* __restrict__ err) {
-  // Each 32-lane group walks a CONTIGUOUS span of triples and keeps one run
-  // per table side: the current user, positive and negative rows are read
-  // once per run of equal ids, and their gradient contributions are summed in
-  // registers and added with ONE row of atomics when the run ends. The
-  // reference's own batches are such runs (PairWiseDataset's m x m product:
-  // one user for m*m triples, each positive repeated m times in a row,
-  // base_datasets.py:94-107), so the atomics per triple drop from 3 rows to
-  // ~1 there; uniform random triples (runs of 1) cost what they did.
+  // One run per table side over this group's span of triples, as dr::RowRun
+  // (row_runs.h) keeps it, here in the text this kernel had before that header:
+  // on three RowRuns hipcc contracts the user-gradient sum differently (other
+  // last bits in grad_user) and the m x m batch measured 1.5 to 4 % slower
+  // than this text (profiles/row_runs/summary.txt).
   const int gl = threadIdx.x & 31;
   const int64_t group = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 5;
   const int64_t b0 = group * span;
@@ -210,9 +200,8 @@ extern "C" int dr_adam_rows(float* param, float* grad, float* exp_avg, float* ex
   const double bc2 = 1.0 - std::pow(beta2, (double)step);
   const double step_size = lr * std::sqrt(bc2) / bc1;
   const int64_t n = n_rows * d;
-  int64_t grid = dr::ceil_div(n, kBlock);
-  if (grid > 256 * 16) grid = 256 * 16;
-  hipLaunchKernelGGL(adam_rows_kernel, dim3((unsigned)grid), dim3(kBlock), 0,
+  const int grid = dr::capped_grid(n, kBlock, 256 * 16);
+  hipLaunchKernelGGL(adam_rows_kernel, dim3(grid), dim3(kBlock), 0,
                      (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, d, rows, n,
                      (float)(1.0 - beta1), (float)(1.0 - beta2), (float)(-step_size), (float)eps,
                      zero_grad);
@@ -231,28 +220,12 @@ extern "C" int dr_bpr_fwd_bwd(const float* user_table, int64_t n_user_rows,
   DR_CHECK_ARG(user_table && item_table && user_id && pos_id && neg_id, "null pointer");
   DR_CHECK_ARG(d >= 1 && d <= 512, "d must be in [1, 512]");
   hipStream_t s = (hipStream_t)stream;
-  // contiguous spans of triples per 32-lane group, up to 8 workgroups per CU
-  constexpr int64_t kGroups = 256 * 8 * (kBlock / 32);
-  // (at least 16 per span, so runs are summed in small batches too)
-  const int64_t span = std::max<int64_t>(16, dr::ceil_div(batch, kGroups));
-  const int64_t grid = dr::ceil_div(dr::ceil_div(batch, span), kBlock / 32);
-#define DR_BPR(EE)                                                                          \
-  hipLaunchKernelGGL(bpr_kernel<EE>, dim3((unsigned)grid), dim3(kBlock), 0, s, user_table,  \
-                     n_user_rows, item_table, n_item_rows, d, user_id, pos_id, neg_id, batch, \
-                     span, grad_scale, loss, hit, grad_user, grad_item, err)
-  switch ((int)dr::ceil_div(d, 32)) {
-    case 1: DR_BPR(1); break;
-    case 2: DR_BPR(2); break;
-    case 3: DR_BPR(3); break;
-    case 4: DR_BPR(4); break;
-    case 5: DR_BPR(5); break;
-    case 6: DR_BPR(6); break;
-    case 7: DR_BPR(7); break;
-    case 8: DR_BPR(8); break;
-    case 9: case 10: case 11: case 12: DR_BPR(12); break;
-    default: DR_BPR(16); break;
-  }
-#undef DR_BPR
+  const dr::SpanPlan plan = dr::span_plan(batch, kBlock);
+  dr::for_row_elems<1, 2, 3, 4, 5, 6, 7, 8, 12, 16>(dr::ceil_div(d, 32), [&](auto E) {
+    hipLaunchKernelGGL(bpr_kernel<decltype(E)::value>, dim3((unsigned)plan.grid), dim3(kBlock), 0,
+                       s, user_table, n_user_rows, item_table, n_item_rows, d, user_id, pos_id,
+                       neg_id, batch, plan.span, grad_scale, loss, hit, grad_user, grad_item, err);
+  });
   DR_CHECK_LAUNCH();
   return DR_OK;
 }
@@ -270,9 +243,8 @@ extern "C" int dr_adam_dense(float* param, const float* grad, float* exp_avg, fl
   const float bc2_sqrt = (float)std::pow(bc2, 0.5);  // Python: bias_correction2 ** 0.5
   const float w1 = (float)(1.0 - beta1);
   const float w2 = (float)(1.0 - beta2);
-  int64_t grid = dr::ceil_div(n, kBlock);
-  if (grid > 256 * 16) grid = 256 * 16;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream,
+  const int grid = dr::capped_grid(n, kBlock, 256 * 16);
+  hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream,
                      param, grad, exp_avg, exp_avg_sq, n, w1, (float)beta2, w2, bc2_sqrt, neg_step,
                      (float)eps, (float)weight_decay);
   DR_CHECK_LAUNCH();

@@ -18,10 +18,11 @@
 // IndexError): an invalid pair reads no row of its own, writes NaN (forward)
 // or adds nothing (backward), and is counted in *err when err is not NULL.
 // Row ids are int32 after the check (tables of up to 2^31 rows).
-#include "common.h"
+#include "row_runs.h"
 
 namespace {
 
+using dr::in_rows;
 using dr::kWave;
 
 template <typename T>
@@ -53,8 +54,7 @@ struct Vec16<__bf16> {
 constexpr int kUnroll = 4;
 constexpr int kGatherUW = 8;  // pairs in flight per lane group when a lane holds one 16-B row chunk
 constexpr int kBlock = 256;
-
-__device__ __forceinline__ bool in_rows(int64_t r, int64_t n) { return r >= 0 && r < n; }
+constexpr int kGridCap = 256 * 8;  // up to 8 workgroups per CU; the kernels grid-stride the rest
 
 // G lanes per pair; lane gl covers 16-B chunks gl, gl + G, ... (CH of them)
 // of the row's `chunks`. The pairs are cut into blocks of G consecutive
@@ -193,46 +193,34 @@ __global__ __launch_bounds__(kBlock) void gather_dot_generic(
   }
 }
 
-// Backward with the BPR kernel's contiguous row layout: a group of 32 lanes
-// owns a pair and lane l handles elements l, l+32, ..., so every load and
-// every atomic wave-instruction covers two contiguous 128-B row segments (the
-// shape at which global_atomic_add_f32 runs at full rate; 16-B-per-lane
-// chunks scatter each atomic instruction over 16-B strides and measured 3.9x
-// slower). EPL = elements per lane = ceil(d / 32), any d <= 512.
+// Backward in the row layout of row_runs.h, a 32-lane group per pair and
+// grid-strided (no runs). EPL = elements per lane = ceil(d / 32), any d <= 512.
 template <int EPL>
 __global__ __launch_bounds__(kBlock) void gather_dot_bwd_rows(
     const float* __restrict__ U, int64_t nu, const float* __restrict__ I, int64_t ni, int64_t d,
     const int64_t* __restrict__ uid, const int64_t* __restrict__ iid, int64_t n,
     const float* __restrict__ gout, float* __restrict__ gU, float* __restrict__ gI,
     int32_t* __restrict__ err) {
-  const int gl = threadIdx.x & 31;
-  const int64_t group = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 5;
+  const int gl = dr::row_lane();
   const int64_t ngroups = (int64_t)gridDim.x * (kBlock / 32);
   int bad = 0;
-  for (int64_t p = group; p < n; p += ngroups) {
+  for (int64_t p = dr::row_group(kBlock); p < n; p += ngroups) {
     const int64_t u = uid[p], i = iid[p];
     if (!in_rows(u, nu) || !in_rows(i, ni)) {  // uniform in the 32-lane group
       bad += gl == 0 ? 1 : 0;
       continue;
     }
     const float g = gout[p];
-    const float* ur = U + u * d;
-    const float* ir = I + i * d;
-    float uv[EPL], iv[EPL];
+    float uv[EPL], iv[EPL], du[EPL], di[EPL];
+    dr::load_row(U + u * d, d, gl, uv);
+    dr::load_row(I + i * d, d, gl, iv);
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
-      const int64_t c = gl + 32 * e;
-      uv[e] = c < d ? ur[c] : 0.f;
-      iv[e] = c < d ? ir[c] : 0.f;
+      du[e] = g * iv[e];
+      di[e] = g * uv[e];
     }
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      const int64_t c = gl + 32 * e;
-      if (c < d) {
-        if (gU) atomicAdd(gU + u * d + c, g * iv[e]);
-        if (gI) atomicAdd(gI + i * d + c, g * uv[e]);
-      }
-    }
+    if (gU) dr::atomic_add_row(gU, u, d, gl, du);
+    if (gI) dr::atomic_add_row(gI, i, d, gl, di);
   }
   if (bad && err) atomicAdd(err, bad);
 }
@@ -259,13 +247,6 @@ __global__ __launch_bounds__(kBlock) void gather_dot_bwd_generic(
   }
 }
 
-int grid_for(int64_t items, int per_block) {
-  int64_t g = dr::ceil_div(items, per_block);
-  if (g > 256 * 8) g = 256 * 8;  // grid-stride the rest (Guideline 11)
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 template <typename T>
 int launch_fwd(const T* U, int64_t nu, const T* I, int64_t ni, int64_t d, const int64_t* uid,
                const int64_t* iid, int64_t n, float* out, int32_t* err, hipStream_t s) {
@@ -273,7 +254,7 @@ int launch_fwd(const T* U, int64_t nu, const T* I, int64_t ni, int64_t d, const 
   const int64_t chunks = d % NV == 0 ? d / NV : -1;  // 16-B chunks per row
   auto go = [&](auto kern, int G) {
     // blocks of G pairs dealt cyclically, up to 8 workgroups per CU
-    const int grid = grid_for(dr::ceil_div(dr::ceil_div(n, G), kBlock / G), 1);
+    const int grid = dr::capped_grid(dr::ceil_div(n, G), kBlock / G, kGridCap);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, U, nu, I, ni, d, (int)chunks, uid,
                        iid, n, out, err);
   };
@@ -290,7 +271,7 @@ int launch_fwd(const T* U, int64_t nu, const T* I, int64_t ni, int64_t d, const 
   else if (chunks > 0 && chunks <= 128) DR_RUNS(64, 2);
 #undef DR_RUNS
   else {
-    const int grid = grid_for(n, kBlock / kWave);
+    const int grid = dr::capped_grid(n, kBlock / kWave, kGridCap);
     hipLaunchKernelGGL(gather_dot_generic<T>, dim3(grid), dim3(kBlock), 0, s, U, nu, I, ni, d,
                        uid, iid, n, out, err);
   }
@@ -335,24 +316,14 @@ extern "C" int dr_gather_dot_backward(const float* user_table, int64_t n_user_ro
   DR_CHECK_ARG(user_table && item_table && user_id && item_id && grad_out, "null pointer");
   hipStream_t s = (hipStream_t)stream;
   if (d <= 512) {
-    const int grid = grid_for(n, kBlock / 32);
-#define DR_BWD(EE)                                                                          \
-  hipLaunchKernelGGL(gather_dot_bwd_rows<EE>, dim3(grid), dim3(kBlock), 0, s, user_table,   \
-                     n_user_rows, item_table, n_item_rows, d, user_id, item_id, n, grad_out, \
-                     grad_user, grad_item, err)
-    switch ((int)dr::ceil_div(d, 32)) {
-      case 1: DR_BWD(1); break;
-      case 2: DR_BWD(2); break;
-      case 3: DR_BWD(3); break;
-      case 4: DR_BWD(4); break;
-      case 5: case 6: DR_BWD(6); break;
-      case 7: case 8: DR_BWD(8); break;
-      case 9: case 10: case 11: case 12: DR_BWD(12); break;
-      default: DR_BWD(16); break;
-    }
-#undef DR_BWD
+    const int grid = dr::capped_grid(n, kBlock / 32, kGridCap);
+    dr::for_row_elems<1, 2, 3, 4, 6, 8, 12, 16>(dr::ceil_div(d, 32), [&](auto E) {
+      hipLaunchKernelGGL(gather_dot_bwd_rows<decltype(E)::value>, dim3(grid), dim3(kBlock), 0, s,
+                         user_table, n_user_rows, item_table, n_item_rows, d, user_id, item_id, n,
+                         grad_out, grad_user, grad_item, err);
+    });
   } else {
-    const int grid = grid_for(n, kBlock / kWave);
+    const int grid = dr::capped_grid(n, kBlock / kWave, kGridCap);
     hipLaunchKernelGGL(gather_dot_bwd_generic, dim3(grid), dim3(kBlock), 0, s, user_table,
                        n_user_rows, item_table, n_item_rows, d, user_id, item_id, n, grad_out,
                        grad_user, grad_item, err);

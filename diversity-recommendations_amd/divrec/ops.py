@@ -45,6 +45,24 @@ def _grad_like(grad: Optional[torch.Tensor], table: torch.Tensor, name: str) -> 
               f"{name} must be a contiguous fp32 tensor shaped like its table")
 
 
+def _table_pair(user_table: torch.Tensor, item_table: torch.Tensor, dtypes, dtype_msg: str) -> None:
+    """Two contiguous 2-D tables of one width, each of a dtype in ``dtypes``."""
+    _need(user_table.dim() == 2 and item_table.dim() == 2, "tables must be 2-D")
+    _need(user_table.size(1) == item_table.size(1), "tables must share embedding_dim")
+    _need(user_table.dtype in dtypes and item_table.dtype in dtypes, dtype_msg)
+    _contig(user_table, "user_table"), _contig(item_table, "item_table")
+
+
+_IDS_MSG = "ids must be 1-D int64 of equal length"
+
+
+def _id_columns(ids, dtype_msg: str = _IDS_MSG, shape_msg: str = _IDS_MSG):
+    """1-D int64 id tensors of equal length, made contiguous."""
+    _need(all(t.dtype == torch.int64 for t in ids), dtype_msg)
+    _need(all(t.dim() == 1 and t.shape == ids[0].shape for t in ids), shape_msg)
+    return tuple(t.contiguous() for t in ids)
+
+
 def _user_ids(user_ids: torch.Tensor) -> torch.Tensor:
     _need(user_ids.dtype == torch.int64 and user_ids.dim() == 1, "user_ids must be 1-D int64")
     return user_ids.contiguous()
@@ -67,14 +85,11 @@ def gather_dot(
     otherwise the count goes to the caller's ``err`` (may be None), which the
     caller reads when it chooses (divrec._backend.raise_if_out_of_range)."""
     dev = B.require_device(user_table, item_table, user_id, item_id)
-    _need(user_table.dim() == 2 and item_table.dim() == 2, "tables must be 2-D")
-    _need(user_table.size(1) == item_table.size(1), "tables must share embedding_dim")
     _need(user_table.dtype == item_table.dtype, "tables must share dtype")
-    _need(user_table.dtype in (torch.float32, torch.bfloat16), "tables must be fp32 or bf16")
-    _need(user_id.dtype == torch.int64 and item_id.dtype == torch.int64, "ids must be int64")
-    _need(user_id.dim() == 1 and user_id.shape == item_id.shape, "ids must be 1-D, same length")
-    _contig(user_table, "user_table"), _contig(item_table, "item_table")
-    user_id, item_id = user_id.contiguous(), item_id.contiguous()
+    _table_pair(user_table, item_table, (torch.float32, torch.bfloat16),
+                "tables must be fp32 or bf16")
+    user_id, item_id = _id_columns((user_id, item_id), "ids must be int64",
+                                   "ids must be 1-D, same length")
     out = torch.empty(user_id.numel(), dtype=torch.float32, device=dev)
     err, own = _counter(dev, err, check)
     rc = B.lib().dr_gather_dot(
@@ -513,16 +528,10 @@ def bpr_fwd_bwd(
     IndexError; otherwise the count goes to the caller's ``err`` (may be None),
     checked by the caller (pair_wise_train_loop: once per epoch)."""
     dev = B.require_device(user_table, item_table, user_id, pos_id, neg_id, grad_user, grad_item)
-    _need(user_table.dtype == torch.float32 and item_table.dtype == torch.float32, "fp32 tables")
-    _need(user_table.dim() == 2 and item_table.dim() == 2, "tables must be 2-D")
-    _need(user_table.size(1) == item_table.size(1), "tables must share embedding_dim")
-    _contig(user_table, "user_table"), _contig(item_table, "item_table")
-    for t in (user_id, pos_id, neg_id):
-        _need(t.dtype == torch.int64 and t.dim() == 1 and t.numel() == user_id.numel(),
-              "ids must be 1-D int64 of equal length")
+    _table_pair(user_table, item_table, (torch.float32,), "fp32 tables")
+    user_id, pos_id, neg_id = _id_columns((user_id, pos_id, neg_id))
     n = user_id.numel()
     _grad_like(grad_user, user_table, "grad_user"), _grad_like(grad_item, item_table, "grad_item")
-    user_id, pos_id, neg_id = user_id.contiguous(), pos_id.contiguous(), neg_id.contiguous()
     loss = torch.empty(n, dtype=torch.float32, device=dev)
     hit = torch.empty(n, dtype=torch.int32, device=dev)
     err, own = _counter(dev, err, check)
@@ -559,18 +568,13 @@ def mse_fwd_bwd(
     goes to the caller's ``err`` (may be None), checked by the caller
     (point_wise_train_loop: once per epoch)."""
     dev = B.require_device(user_table, item_table, user_id, item_id, target, grad_user, grad_item)
-    _need(user_table.dtype == torch.float32 and item_table.dtype == torch.float32, "fp32 tables")
-    _need(user_table.dim() == 2 and item_table.dim() == 2, "tables must be 2-D")
-    _need(user_table.size(1) == item_table.size(1), "tables must share embedding_dim")
-    _contig(user_table, "user_table"), _contig(item_table, "item_table")
-    for t in (user_id, item_id):
-        _need(t.dtype == torch.int64 and t.dim() == 1 and t.numel() == user_id.numel(),
-              "ids must be 1-D int64 of equal length")
+    _table_pair(user_table, item_table, (torch.float32,), "fp32 tables")
+    user_id, item_id = _id_columns((user_id, item_id))
     n = user_id.numel()
     _need(target.dtype == torch.float32 and target.dim() == 1 and target.numel() == n,
           "target must be 1-D fp32, one per pair")
     _grad_like(grad_user, user_table, "grad_user"), _grad_like(grad_item, item_table, "grad_item")
-    user_id, item_id, target = user_id.contiguous(), item_id.contiguous(), target.contiguous()
+    target = target.contiguous()
     pred = torch.empty(n, dtype=torch.float32, device=dev)
     loss = torch.empty(n, dtype=torch.float32, device=dev)
     err, own = _counter(dev, err, check)

@@ -457,28 +457,44 @@ def _bpr_fast_path(model, loss, scores) -> bool:
             and (scores is None or all(type(s) is AUCScore for s in scores)))
 
 
-def _bpr_fused_batch(model: MatrixFactorization, user_id, pos, neg, epoch_err):
-    """One batch of the fused BPR path: range checks, then ONE dr_bpr_fwd_bwd
-    that adds the batch's dense gradients into the embeddings' ``.grad`` (the
-    'mean' reduction). No optimizer step. Returns (uid, pid, nid, per-triple
-    losses, hit flags, epoch_err), the ids on the model's device; epoch_err is
-    the epoch's id range counter (made here on the first batch)."""
-    dev = model._device()
-    U, I = model.user_embeddings.weight, model.item_embeddings.weight
-    host = user_id.device.type == "cpu"
-    if host:  # host batches: raise before any compute
-        _backend.host_ids_in_range(user_id, U.size(0), "user_id")
-        _backend.host_ids_in_range(pos, I.size(0), "positive item_id")
-        _backend.host_ids_in_range(neg, I.size(0), "negative item_id")
-    uid, pid, nid = (t.to(dev, torch.int64, non_blocking=True) for t in (user_id, pos, neg))
-    if not host:
-        _device_ids_in_range(uid, U.size(0), (pid, nid), I.size(0))
-    _dense_grads(U, I)
-    epoch_err = _epoch_counter(epoch_err, dev)
-    B = uid.numel()
-    losses_b, hits = ops.bpr_fwd_bwd(U.data, I.data, uid, pid, nid, 1.0 / B, U.grad, I.grad,
-                                     err=epoch_err, check=False)
-    return uid, pid, nid, losses_b, hits, epoch_err
+def _pair_wise_batch(model: RankingModel, loss: PairWiseLoss, scores, fused: bool, batch,
+                     epoch_err):
+    """One batch's pairwise part, up to the optimizer step (not taken here):
+    the batch's gradients end up in ``.grad``. ``fused``: range checks, then
+    ONE dr_bpr_fwd_bwd that adds the dense gradients of the 'mean' reduction
+    into the embeddings' ``.grad``; otherwise the model's forward and autograd.
+    Returns (ids, loss value, score row, epoch_err): ids = (uid, pid, nid) on
+    the model's device (None on the generic path), the score row a tensor of
+    the reduced ``scores`` (None without scores), epoch_err the epoch's id
+    range counter (made here on the first fused batch)."""
+    user_id, pos, neg, uf, pf, nf = batch
+    if fused:
+        dev = model._device()
+        U, I = model.user_embeddings.weight, model.item_embeddings.weight
+        host = user_id.device.type == "cpu"
+        if host:  # host batches: raise before any compute
+            _backend.host_ids_in_range(user_id, U.size(0), "user_id")
+            _backend.host_ids_in_range(pos, I.size(0), "positive item_id")
+            _backend.host_ids_in_range(neg, I.size(0), "negative item_id")
+        ids = tuple(t.to(dev, torch.int64, non_blocking=True) for t in (user_id, pos, neg))
+        if not host:
+            _device_ids_in_range(ids[0], U.size(0), ids[1:], I.size(0))
+        _dense_grads(U, I)
+        epoch_err = _epoch_counter(epoch_err, dev)
+        B = ids[0].numel()
+        losses_b, hits = ops.bpr_fwd_bwd(U.data, I.data, *ids, 1.0 / B, U.grad, I.grad,
+                                         err=epoch_err, check=False)
+        loss_value = torch.sum(losses_b, dim=0) / B
+        # AUCScore.pair_wise = the hit flags, reduced as each score says
+        row = [s.reduce_loss_values(hits).double() for s in scores or ()]
+    else:
+        ids = None
+        positives = model(user_id, pos, uf, pf)
+        negatives = model(user_id, neg, uf, nf)
+        loss_value = loss(positives, negatives)
+        loss_value.backward()
+        row = [s(positives.detach(), negatives.detach()).double() for s in scores or ()]
+    return ids, loss_value.detach(), torch.stack(row) if row else None, epoch_err
 
 
 def pair_wise_train_loop(dataset: PairWiseDataset, model: RankingModel, loss: PairWiseLoss,
@@ -491,33 +507,18 @@ def pair_wise_train_loop(dataset: PairWiseDataset, model: RankingModel, loss: Pa
     n_scores = len(scores) if scores is not None else 0
     batch_losses, batch_scores = [], []
     fused = _bpr_fast_path(model, loss, scores)
-    adam = _plain_adam(optimizer)
+    adam = fused and _plain_adam(optimizer)  # the generic path steps the optimizer itself
     lazy = fused and _plain_sparse_adam(optimizer)
     epoch_err = None  # id range errors of the fused kernel on device batches
-    for user_id, pos, neg, uf, pf, nf in dataset.loader(**loader_params):
-        if fused:
-            U, I = model.user_embeddings.weight, model.item_embeddings.weight
-            uid, pid, nid, losses_b, hits, epoch_err = _bpr_fused_batch(model, user_id, pos, neg,
-                                                                        epoch_err)
-            B = uid.numel()
-            loss_value = torch.sum(losses_b, dim=0) / B
-            _optimizer_step(optimizer, adam, lazy, lambda: {
-                U: torch.unique(uid), I: torch.unique(torch.cat([pid, nid]))})
-            batch_losses.append(loss_value.detach())
-            if n_scores:  # AUCScore.pair_wise = the hit flags, reduced as each score says
-                batch_scores.append(torch.stack(
-                    [s.reduce_loss_values(hits).double() for s in scores]))
-        else:
-            positives = model(user_id, pos, uf, pf)
-            negatives = model(user_id, neg, uf, nf)
-            loss_value = loss(positives, negatives)
-            loss_value.backward()
-            optimizer.step()
-            optimizer.zero_grad()
-            batch_losses.append(loss_value.detach())
-            if n_scores:
-                batch_scores.append(torch.stack(
-                    [s(positives.detach(), negatives.detach()).double() for s in scores]))
+    for batch in dataset.loader(**loader_params):
+        ids, loss_value, row, epoch_err = _pair_wise_batch(model, loss, scores, fused, batch,
+                                                           epoch_err)
+        _optimizer_step(optimizer, adam, lazy, lambda: {
+            model.user_embeddings.weight: torch.unique(ids[0]),
+            model.item_embeddings.weight: torch.unique(torch.cat(ids[1:]))})
+        batch_losses.append(loss_value)
+        if n_scores:
+            batch_scores.append(row)
     _backend.raise_if_out_of_range(epoch_err, "pair_wise_train_loop")
     return _pair_wise_epoch_means(batch_losses, batch_scores, n_scores)
 
@@ -582,25 +583,14 @@ def diversity_pair_wise_train_loop(dataset: PairWiseDataset, model: MatrixFactor
     lazy = fused and _plain_sparse_adam(optimizer)
     dev = model._device()
     epoch_err = None  # id range errors of the kernels on device batches
-    for user_id, pos, neg, uf, pf, nf in dataset.loader(**loader_params):
+    for batch in dataset.loader(**loader_params):
         U, I = model.user_embeddings.weight, model.item_embeddings.weight
-        if fused:
-            uid, pid, nid, losses_b, hits, epoch_err = _bpr_fused_batch(model, user_id, pos, neg,
-                                                                        epoch_err)
-            loss_value = torch.sum(losses_b, dim=0) / uid.numel()
-            if n_scores:
-                batch_scores.append(torch.stack(
-                    [s.reduce_loss_values(hits).double() for s in scores]))
-        else:
-            positives = model(user_id, pos, uf, pf)
-            negatives = model(user_id, neg, uf, nf)
-            loss_value = loss(positives, negatives)
-            loss_value.backward()
-            uid = user_id.to(dev, torch.int64)
-            if n_scores:
-                batch_scores.append(torch.stack(
-                    [s(positives.detach(), negatives.detach()).double() for s in scores]))
-        batch_losses.append(loss_value.detach())
+        ids, loss_value, row, epoch_err = _pair_wise_batch(model, loss, scores, fused, batch,
+                                                           epoch_err)
+        uid = ids[0] if fused else batch[0].to(dev, torch.int64)
+        batch_losses.append(loss_value)
+        if n_scores:
+            batch_scores.append(row)
         # the regulariser: the lists of the batch's users under the current
         # parameters, their ILD, and its gradient added to the item table's
         users = torch.unique(uid)
@@ -614,7 +604,7 @@ def diversity_pair_wise_train_loop(dataset: PairWiseDataset, model: MatrixFactor
                                    err=epoch_err, check=False)
         # the lists' items are touched rows too: their gradient rows are zeroed
         _optimizer_step(optimizer, adam, lazy, lambda: {
-            U: users, I: torch.unique(torch.cat([pid, nid, items.reshape(-1)]))})
+            U: users, I: torch.unique(torch.cat([*ids[1:], items.reshape(-1)]))})
     _backend.raise_if_out_of_range(epoch_err, "diversity_pair_wise_train_loop")
     mean_loss, means = _pair_wise_epoch_means(batch_losses, batch_scores, n_scores)
     ilds = torch.stack(batch_ilds).double().cpu().tolist()

@@ -148,22 +148,45 @@ def test_ids_out_of_range_raise_index_error():
     assert not torch.isnan(vals[0]) and torch.isnan(vals[1])
 
 
-@pytest.mark.parametrize("d", [32, 64, 100, 128, 300])
-def test_gather_dot_backward(d):
+def _gather_dot_backward_case(d, bad=()):
+    """40 x 60 rows, 2000 pairs, ``bad`` = (pair, column, id) entries put out of
+    range; the gradients against float64 sums over the pairs left in range.
+    Returns the call's id-range count."""
     rng = np.random.default_rng(3 + d)
     U = rng.standard_normal((40, d)).astype(np.float32)
     I = rng.standard_normal((60, d)).astype(np.float32)
     uid, iid = rng.integers(0, 40, 2000), rng.integers(0, 60, 2000)
+    for p, col, value in bad:
+        (uid, iid)[col][p] = value
     go = rng.standard_normal(2000).astype(np.float32)
     gU = torch.zeros(40, d, device=DEV)
     gI = torch.zeros(60, d, device=DEV)
+    err = _backend.error_counter(torch.device(DEV))
     ops.gather_dot_backward(torch.from_numpy(U).to(DEV), torch.from_numpy(I).to(DEV),
                             torch.from_numpy(uid).to(DEV), torch.from_numpy(iid).to(DEV),
-                            torch.from_numpy(go).to(DEV), gU, gI)
+                            torch.from_numpy(go).to(DEV), gU, gI, err=err)
+    ok = (uid >= 0) & (uid < 40) & (iid >= 0) & (iid < 60)
+    uid, iid, go = uid[ok], iid[ok], go[ok]
     rU = np.zeros((40, d)); np.add.at(rU, uid, go[:, None].astype(np.float64) * I[iid])
     rI = np.zeros((60, d)); np.add.at(rI, iid, go[:, None].astype(np.float64) * U[uid])
     assert np.allclose(gU.cpu().numpy(), rU, rtol=1e-4, atol=1e-4)
     assert np.allclose(gI.cpu().numpy(), rI, rtol=1e-4, atol=1e-4)
+    return int(err.item())
+
+
+@pytest.mark.parametrize("d", [32, 64, 96, 100, 128, 160, 224, 300, 512, 513])
+def test_gather_dot_backward(d):
+    """Every instance of gather_dot_bwd_rows (1, 2, 3, 4, 6, 8, 12 and 16
+    elements per lane: 32, 64, 96, 100 and 128, 160, 224, 300, 512) and the
+    d > 512 kernel (513)."""
+    assert _gather_dot_backward_case(d) == 0
+
+
+@pytest.mark.parametrize("d", [100, 513])
+def test_gather_dot_backward_bad_ids_add_nothing(d):
+    """A user id past the table and a negative item id: both pairs are counted
+    and add nothing; the other pairs' gradients are whole."""
+    assert _gather_dot_backward_case(d, bad=[(7, 0, 40), (1500, 1, -1)]) == 2
 
 
 # --------------------------------------------------------------------------- score_topk

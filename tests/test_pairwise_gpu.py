@@ -73,6 +73,12 @@ def test_bpr_every_instance(d):
     bpr_against_f64(bpr_case(d), f"instance d={d}")
 
 
+def test_bpr_eight_element_instance():
+    """d = 256, E = 8: the instance no width of BPR_WIDTHS reaches (E = 4 runs
+    at d = 100 below)."""
+    bpr_against_f64(bpr_case(256), "instance d=256")
+
+
 def test_bpr_saturated_scores():
     """|x| up to about 260: exp(-|x|) underflows, the loss is -x or 0 and the
     gradient weight 1 or 0; nothing becomes NaN or Inf."""

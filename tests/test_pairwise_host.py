@@ -208,6 +208,10 @@ def test_bpr_inputs_leave_the_bounds_room(d):
     assert 9 <= inside <= 19 and inside - same <= 2
 
 
+def test_bpr_eight_element_inputs_leave_the_bounds_room():
+    _bpr_inputs_hold(*bpr_case(256), cap=0.01, what="d=256 emulation")
+
+
 def test_bpr_saturated_inputs_leave_the_bounds_room():
     """d = 32 with tables scaled by 3.0: |x| reaches about 260, where
     exp(-|x|) underflows to 0 and the loss is -x or 0."""

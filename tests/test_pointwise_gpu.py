@@ -14,6 +14,7 @@ import torch
 
 from divrec import _backend, datasets, losses, models, ops, train
 from divrec.train import utils as train_utils
+from pairwise_checks import BPR_WIDTHS
 from pointwise_checks import load, loop_data, mse_step_f64
 
 pytestmark = pytest.mark.gpu
@@ -59,11 +60,11 @@ def random_batch(rng, nu, ni, B):
 
 
 # --------------------------------------------------------------------------- kernel
-@pytest.mark.parametrize("d", [33, 100, 128, 300, 512])
+@pytest.mark.parametrize("d", sorted({*BPR_WIDTHS, 100, 128, 256}))
 def test_mse_kernel_against_float64(d):
-    """One partial 32-lane slice past the first (33), the reference's width
-    (100), 128, the 9-12-element instance with a masked tail (300) and the
-    widest instance (512)."""
+    """Every instance, as for bpr_kernel (pairwise_checks.BPR_WIDTHS: 1 to 3, 5
+    to 7, 12 and 16 elements per lane, with masked tails), and 4 and 8
+    elements: the reference's width (100), 128 and 256."""
     rng = np.random.default_rng(d)
     U, I = tables(rng, 200, 300, d)
     check_against_f64(U, I, *random_batch(rng, 200, 300, 4096), what="random")
