@@ -87,6 +87,10 @@ SIGNATURES = {
     "dr_rank_metrics": (_i32, [_p, _i32, _i64, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "dr_catalog_histogram": (_i32, [_p, _i32, _i64, _i32, _i64, _p, _p, _p]),
     "dr_als_solve": (_i32, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _f32, _f32, _p, _p, _p]),
+    "dr_csr_row_sum_chunk": (_i32, []),
+    "dr_csr_row_sum_workspace": (_sz, [_i64, _i32]),
+    "dr_csr_row_sum": (_i32, [_p, _i64, _i32, _p, _p, _p, _i64, _p, _i64, _i64, _p, _i32, _p, _sz,
+                              _p, _p]),
 }
 
 _LIB: Optional[ctypes.CDLL] = None

@@ -9,11 +9,13 @@ from .base_datasets import (
     RankingRow,
     interaction_csr,
 )
+from .feature_maps import FeatureCSR, feature_csr
 from .storages import Features, UserItemInteractionsDataset
 
 __all__ = [
     "DevicePairWiseDataset",
     "DevicePointWiseDataset",
+    "FeatureCSR",
     "Features",
     "UserItemInteractionsDataset",
     "PairWiseRow",
@@ -22,5 +24,6 @@ __all__ = [
     "PointWiseDataset",
     "RankingDataset",
     "RankingRow",
+    "feature_csr",
     "interaction_csr",
 ]

@@ -75,86 +75,77 @@ def _ids_for(model_device: torch.device, ids, n_rows: int, what: str):
     return _on_device(model_device, ids), host
 
 
-class MatrixFactorization(RankingModel):
-    def __init__(self, no_users: int, no_items: int, embedding_dim: int):
-        torch.nn.Module.__init__(self)
-        self.no_users = no_users
-        self.no_items = no_items
-        self.embedding_dim = embedding_dim
-        self.user_embeddings = torch.nn.Embedding(no_users, embedding_dim)
-        self.item_embeddings = torch.nn.Embedding(no_items, embedding_dim)
+def _scan_form(table: torch.Tensor, dt: torch.dtype, w: int) -> torch.Tensor:
+    """``table`` as a scan operand of dtype ``dt`` and width ``w``: itself when
+    it already is one, else a converted / zero-padded copy."""
+    if dt == table.dtype and w == table.size(1) and table.is_contiguous():
+        return table.detach()
+    with torch.no_grad():
+        return ops.pad_columns(table.detach().to(dt).contiguous(), w)
+
+
+class _TableModel(RankingModel):
+    """A model whose score is the dot product of a user row and an item row of
+    two fp32 tables of width ``embedding_dim``, ``no_users`` and ``no_items``
+    rows long. ONE hook says what those tables are, ``_tables``; everything
+    that scans them (``scoring_tables``, ``score_topk``, ``recommend_diverse``)
+    is written once, here, for every such model."""
 
     def _device(self) -> torch.device:
-        dev = self.user_embeddings.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError(
-                "MatrixFactorization runs on the divrec HIP backend: move the model to a "
-                "ROCm device first (model.to('cuda')); there is no CPU path"
-            )
-        return dev
+        raise NotImplementedError
 
-    def forward(
-        self,
-        user_id: torch.LongTensor,
-        item_id: torch.LongTensor,
-        user_features: Optional[torch.Tensor] = None,
-        item_features: Optional[torch.Tensor] = None,
-    ) -> torch.Tensor:
-        dev = self._device()
-        uid, hu = _ids_for(dev, user_id, self.user_embeddings.num_embeddings, "user_id")
-        iid, hi = _ids_for(dev, item_id, self.item_embeddings.num_embeddings, "item_id")
-        return _GatherDot.apply(self.user_embeddings.weight, self.item_embeddings.weight, uid, iid,
-                                hu and hi)
+    def _tables(self, users: bool = True, items: bool = True):
+        """The tables of this model: (user table or None, item table or None),
+        fp32 [rows, embedding_dim] on the model's device, as the parameters
+        stand now. A side not asked for may be None (it may cost a kernel)."""
+        raise NotImplementedError
 
     def scoring_tables(self, precision: str = "fp32") -> Tuple[torch.Tensor, torch.Tensor]:
         """The (user, item) tables score_topk scans at ``precision``: the
-        parameters themselves when their dtype and width already have a scan
-        instance, else a converted / zero-padded copy made by this call (never
-        cached: an update through ``weight.data`` or a raw-pointer optimizer
-        bumps no version a cache could key on)."""
+        model's tables themselves when their dtype and width already have a
+        scan instance, else a converted / zero-padded copy made by this call.
+        Never cached, for any model: an update through ``weight.data`` or a
+        raw-pointer optimizer bumps no version a cache could key on (ADVICE
+        r2), so a kept copy, or a kept composed table of a feature model, could
+        not know that it is stale."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
         self._device()
-        U, I = self.user_embeddings.weight, self.item_embeddings.weight
         dt = PRECISIONS[precision]
-        w = ops.score_width(dt, U.size(1))
-        if dt == U.dtype and w == U.size(1) and U.is_contiguous() and I.is_contiguous():
-            return U.detach(), I.detach()
-        with torch.no_grad():
-            return (ops.pad_columns(U.detach().to(dt).contiguous(), w),
-                    ops.pad_columns(I.detach().to(dt).contiguous(), w))
+        w = ops.score_width(dt, self.embedding_dim)
+        U, I = self._tables()
+        return _scan_form(U, dt, w), _scan_form(I, dt, w)
 
     def bf16_tables(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """bf16 copies of both tables (the fast scoring mode's operands)."""
         return self.scoring_tables("bf16")
 
-    def _user_side(self, user_vectors: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
-        """``user_vectors`` (fp32 [n, embedding_dim]) as the user table of a
-        scan beside ``like``, the model's own: its dtype and padded width."""
-        if (user_vectors.dim() != 2 or user_vectors.size(1) != self.embedding_dim
-                or user_vectors.dtype != torch.float32):
-            raise ValueError(f"user_vectors must be fp32 [n, {self.embedding_dim}], got "
-                             f"{user_vectors.dtype} {tuple(user_vectors.shape)}")
-        rows = user_vectors.detach().to(like.device, like.dtype).contiguous()
-        return ops.pad_columns(rows, like.size(1))
+    def _side(self, vectors: torch.Tensor, what: str, dev: torch.device, dt: torch.dtype,
+              w: int) -> torch.Tensor:
+        """``vectors`` (fp32 [n, embedding_dim]) as one side of a scan beside
+        the model's own table: on its device, of its dtype and padded width."""
+        if (vectors.dim() != 2 or vectors.size(1) != self.embedding_dim
+                or vectors.dtype != torch.float32):
+            raise ValueError(f"{what} must be fp32 [n, {self.embedding_dim}], got "
+                             f"{vectors.dtype} {tuple(vectors.shape)}")
+        return ops.pad_columns(vectors.detach().to(dev, dt).contiguous(), w)
 
-    @torch.no_grad()
-    def fold_in_users(self, rowptr: torch.Tensor, items: torch.Tensor,
-                      weights: Optional[torch.Tensor] = None, alpha: float = 40.0,
-                      reg: float = 0.1) -> torch.Tensor:
-        """Embeddings of users the model has never seen, from their histories
-        (CSR: rowptr int64 [n + 1], items int32, ``weights`` fp32 or None):
-        fp32 [n, embedding_dim], each row the ALS solve of that history against
-        the model's item table (``ops.als_solve``; ``alpha`` and ``reg`` as in
-        ``als_train_loop``). The rows go to ``score_topk`` and
-        ``recommend_diverse`` as ``user_vectors``. An item id outside the item
-        table raises IndexError."""
+    def _scan_sides(self, precision: str, user_vectors, item_vectors, users: bool = True):
+        """(user side, item side) of a scan at ``precision``: the caller's
+        vectors where given, else the model's table (``users=False``: no user
+        side at all)."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
         dev = self._device()
-        if self.embedding_dim > ops.ALS_WIDTHS[-1]:
-            raise ValueError(f"fold_in_users supports embedding_dim <= {ops.ALS_WIDTHS[-1]}")
-        w = None if weights is None else weights.to(dev, torch.float32)
-        return ops.als_solve(self.item_embeddings.weight.detach(), rowptr.to(dev, torch.int64),
-                             items.to(dev, torch.int32), w, alpha=alpha, reg=reg)
+        dt = PRECISIONS[precision]
+        w = ops.score_width(dt, self.embedding_dim)
+        U, I = self._tables(users=users and user_vectors is None, items=item_vectors is None)
+        if users:
+            U = (_scan_form(U, dt, w) if user_vectors is None
+                 else self._side(user_vectors, "user_vectors", dev, dt, w))
+        I = (_scan_form(I, dt, w) if item_vectors is None
+             else self._side(item_vectors, "item_vectors", dev, dt, w))
+        return U, I
 
     @torch.no_grad()
     def score_topk(
@@ -166,6 +157,7 @@ class MatrixFactorization(RankingModel):
         n_items: Optional[int] = None,
         *,
         user_vectors: Optional[torch.Tensor] = None,
+        item_vectors: Optional[torch.Tensor] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k items of each user (all users, or ``user_ids``) over the
         catalog (the first ``n_items`` item rows; default all): (items int64
@@ -175,13 +167,15 @@ class MatrixFactorization(RankingModel):
         reference's arithmetic) or "bf16" (fast mode). ``user_vectors`` (fp32
         [n, embedding_dim], e.g. ``fold_in_users``): these rows are the user
         side of the scan instead of the model's user table, converted and
-        padded like ``scoring_tables``; ``user_ids`` must then be None."""
+        padded like ``scoring_tables``; ``user_ids`` must then be None.
+        ``item_vectors`` (fp32 [n, embedding_dim]): these rows are the CATALOG
+        of the call instead of the model's item table, item id = row number
+        (e.g. ``FeatureMatrixFactorization.compose_items(new_csr)``: items the
+        model has never seen)."""
         if user_vectors is not None and user_ids is not None:
             raise ValueError("user_vectors are the users to score: user_ids must be None")
         dev = self._device()
-        U, I = self.scoring_tables(precision)
-        if user_vectors is not None:
-            U = self._user_side(user_vectors, U)
+        U, I = self._scan_sides(precision, user_vectors, item_vectors)
         if n_items is not None:
             I = I[: int(n_items)]
         uids = None if user_ids is None else _on_device(dev, user_ids)
@@ -207,6 +201,7 @@ class MatrixFactorization(RankingModel):
         user_profile: Optional[torch.Tensor] = None,
         n_labels: Optional[int] = None,
         user_vectors: Optional[torch.Tensor] = None,
+        item_vectors: Optional[torch.Tensor] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Diversity re-ranked lists: the top-``candidates`` items of each user
         (``score_topk`` with the same ``user_ids`` / ``exclude`` / ``precision``
@@ -219,7 +214,8 @@ class MatrixFactorization(RankingModel):
         ``n_labels``, when given, must equal G <= 64) and uses no item rows.
         ``user_vectors`` (fp32 [n, embedding_dim], e.g. ``fold_in_users``)
         replaces the model's users as in ``score_topk``; ``user_ids`` must
-        then be None.
+        then be None; ``item_vectors`` (fp32 [n, embedding_dim]) replaces the
+        model's items as the catalog, for the scan and for the re-rank's rows.
         Returns (items int64 [n, k] in pick order,
         scores fp32 [n, k]: the picks' scan scores). A list that ends early
         (fewer eligible candidates than ``k``) holds item -1 / score -inf.
@@ -229,7 +225,9 @@ class MatrixFactorization(RankingModel):
             raise ValueError("user_vectors are the users to score: user_ids must be None")
         if method not in RERANKERS:
             raise ValueError(f"method must be one of {sorted(RERANKERS)}, got {method!r}")
-        catalog = self.no_items if n_items is None else int(n_items)
+        catalog = self.no_items if item_vectors is None else len(item_vectors)
+        if n_items is not None:
+            catalog = int(n_items)
         if not 1 <= k <= candidates <= min(MAX_RERANK_CANDIDATES, catalog):
             raise ValueError(f"need 1 <= k <= candidates <= min({MAX_RERANK_CANDIDATES}, catalog "
                              f"= {catalog}), got k = {k}, candidates = {candidates}")
@@ -254,17 +252,19 @@ class MatrixFactorization(RankingModel):
                              f'"calibrated", not {method!r}')
         cand, cand_scores = self.score_topk(candidates, user_ids=user_ids, exclude=exclude,
                                             precision=precision, n_items=n_items,
-                                            user_vectors=user_vectors)
+                                            user_vectors=user_vectors, item_vectors=item_vectors)
         cand32 = cand.to(torch.int32)
         if method == "calibrated":
             dev = cand.device
             picks, _ = ops.calibrated_rerank(
                 cand32, cand_scores, item_labels[:catalog].to(dev),
                 user_profile.to(dev, torch.float32), k, lam)
-        elif method == "dpp":
-            picks, _ = ops.dpp_rerank(cand32, cand_scores, self.bf16_tables()[1][:catalog], k, lam)
         else:
-            picks = ops.mmr_rerank(cand32, cand_scores, self.bf16_tables()[1][:catalog], k, lam)
+            rows = self._scan_sides("bf16", None, item_vectors, users=False)[1][:catalog]
+            if method == "dpp":
+                picks, _ = ops.dpp_rerank(cand32, cand_scores, rows, k, lam)
+            else:
+                picks = ops.mmr_rerank(cand32, cand_scores, rows, k, lam)
         picks = picks.to(torch.int64)
         # the picks' scan scores: candidate ids are distinct per user, so a pick
         # is found by a search in the user's sorted ids
@@ -272,3 +272,56 @@ class MatrixFactorization(RankingModel):
         at = torch.searchsorted(ids_sorted, picks.contiguous()).clamp_(max=candidates - 1)
         scores = cand_scores.gather(1, order.gather(1, at))
         return picks, scores.masked_fill_(picks < 0, float("-inf"))
+
+
+class MatrixFactorization(_TableModel):
+    def __init__(self, no_users: int, no_items: int, embedding_dim: int):
+        torch.nn.Module.__init__(self)
+        self.no_users = no_users
+        self.no_items = no_items
+        self.embedding_dim = embedding_dim
+        self.user_embeddings = torch.nn.Embedding(no_users, embedding_dim)
+        self.item_embeddings = torch.nn.Embedding(no_items, embedding_dim)
+
+    def _device(self) -> torch.device:
+        dev = self.user_embeddings.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError(
+                "MatrixFactorization runs on the divrec HIP backend: move the model to a "
+                "ROCm device first (model.to('cuda')); there is no CPU path"
+            )
+        return dev
+
+    def _tables(self, users: bool = True, items: bool = True):
+        return self.user_embeddings.weight, self.item_embeddings.weight
+
+    def forward(
+        self,
+        user_id: torch.LongTensor,
+        item_id: torch.LongTensor,
+        user_features: Optional[torch.Tensor] = None,
+        item_features: Optional[torch.Tensor] = None,
+    ) -> torch.Tensor:
+        dev = self._device()
+        uid, hu = _ids_for(dev, user_id, self.user_embeddings.num_embeddings, "user_id")
+        iid, hi = _ids_for(dev, item_id, self.item_embeddings.num_embeddings, "item_id")
+        return _GatherDot.apply(self.user_embeddings.weight, self.item_embeddings.weight, uid, iid,
+                                hu and hi)
+
+    @torch.no_grad()
+    def fold_in_users(self, rowptr: torch.Tensor, items: torch.Tensor,
+                      weights: Optional[torch.Tensor] = None, alpha: float = 40.0,
+                      reg: float = 0.1) -> torch.Tensor:
+        """Embeddings of users the model has never seen, from their histories
+        (CSR: rowptr int64 [n + 1], items int32, ``weights`` fp32 or None):
+        fp32 [n, embedding_dim], each row the ALS solve of that history against
+        the model's item table (``ops.als_solve``; ``alpha`` and ``reg`` as in
+        ``als_train_loop``). The rows go to ``score_topk`` and
+        ``recommend_diverse`` as ``user_vectors``. An item id outside the item
+        table raises IndexError."""
+        dev = self._device()
+        if self.embedding_dim > ops.ALS_WIDTHS[-1]:
+            raise ValueError(f"fold_in_users supports embedding_dim <= {ops.ALS_WIDTHS[-1]}")
+        w = None if weights is None else weights.to(dev, torch.float32)
+        return ops.als_solve(self.item_embeddings.weight.detach(), rowptr.to(dev, torch.int64),
+                             items.to(dev, torch.int32), w, alpha=alpha, reg=reg)

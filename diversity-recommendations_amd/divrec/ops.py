@@ -1023,3 +1023,224 @@ def als_objective(
         sq += (x * x).sum()
     total += float(reg) * (sq + torch.diagonal(g).sum())
     return float(total.item())
+
+
+# --------------------------------------------------------------------------- CSR row sum
+ROW_SUM_CHUNK = 512  # DR_ROW_SUM_CHUNK: entries of a chunk (Appendix-B split rule)
+ROW_SUM_MAX_D = 512  # DR_ROW_SUM_MAX_D
+
+
+class RowSumPlan:
+    """What ``csr_row_sum`` needs from a CSR's ``rowptr`` beyond the pointer,
+    computed once per CSR (``row_sum_plan``): the checked ``rowptr`` itself,
+    the host-side sizes (rows, entries, chunks, long rows) and ``lists``, the
+    int64 tensor of dr_csr_row_sum's five plan lists (include/divrec_hip.h;
+    a single 0 for a CSR without long rows).
+    Keep it as long as the CSR: a call with a plan reads nothing back."""
+
+    __slots__ = ("rowptr", "n_rows", "nnz", "n_chunks", "n_long", "lists")
+
+    def __init__(self, rowptr, n_rows, nnz, n_chunks, n_long, lists):
+        self.rowptr, self.n_rows, self.nnz = rowptr, n_rows, nnz
+        self.n_chunks, self.n_long, self.lists = n_chunks, n_long, lists
+
+
+def row_sum_plan(rowptr: torch.Tensor) -> RowSumPlan:
+    """The plan of ``csr_row_sum`` for the CSR with this ``rowptr`` (int64
+    [n + 1], on any device; torch ops only, so it also runs on the host): the
+    rows longer than ``ROW_SUM_CHUNK`` cut into chunks of that many entries.
+    ONE read-back: rowptr's checks (it rises from 0) and the two list sizes."""
+    _need(rowptr.dtype == torch.int64 and rowptr.dim() == 1 and rowptr.numel() >= 1,
+          "rowptr int64 [n + 1]")
+    rowptr = rowptr.contiguous()
+    n, L, dev = rowptr.numel() - 1, ROW_SUM_CHUNK, rowptr.device
+    lens = rowptr[1:] - rowptr[:-1]
+    is_long = lens > L
+    per_row = torch.where(is_long, (lens + (L - 1)) // L, torch.zeros_like(lens))
+    first, nnz, falls, n_long, n_chunks = torch.stack(
+        [rowptr[0], rowptr[-1], (lens < 0).sum(), is_long.sum(), per_row.sum()]).tolist()
+    _need(first == 0 and falls == 0, "rowptr must rise from 0")
+    if n_long == 0:  # nothing to split: the kernel strides over the rows, no lists
+        return RowSumPlan(rowptr, n, nnz, 0, 0, torch.zeros(1, dtype=torch.int64, device=dev))
+    # long rows first, then the others, each in ascending order, without a
+    # second read-back: one stable sort, cut at the count read above
+    by_kind = torch.sort(is_long.to(torch.int8), descending=True, stable=True).indices
+    long_row, short_row = by_kind[:n_long], by_kind[n_long:]
+    per = per_row[long_row]
+    long_first = torch.zeros(n_long + 1, dtype=torch.int64, device=dev)
+    long_first[1:] = torch.cumsum(per, 0)
+    chunk_row = torch.repeat_interleave(long_row, per, output_size=n_chunks)
+    slot = torch.arange(n_chunks, dtype=torch.int64, device=dev)
+    chunk_k = slot - torch.repeat_interleave(long_first[:-1], per, output_size=n_chunks)
+    chunk_beg = rowptr[chunk_row] + chunk_k * L
+    chunk_len = torch.clamp(rowptr[chunk_row + 1] - chunk_beg, max=L)
+    # every work item (a chunk -> its partial row, a short row -> out), longest first
+    item_row = torch.cat([chunk_row, short_row])
+    item_beg = torch.cat([chunk_beg, rowptr[short_row]])
+    item_slot = torch.cat([slot, torch.full_like(short_row, -1)])
+    order = torch.sort(torch.cat([chunk_len, lens[short_row]]), descending=True, stable=True).indices
+    lists = torch.cat([item_row[order], item_beg[order], item_slot[order], long_row,
+                       long_first]).contiguous()
+    return RowSumPlan(rowptr, n, nnz, n_chunks, n_long, lists)
+
+
+def csr_row_sum(
+    table: torch.Tensor, rowptr: torch.Tensor, cols: torch.Tensor,
+    weights: Optional[torch.Tensor] = None, plan: Optional[RowSumPlan] = None,
+    out_dtype: torch.dtype = torch.float32, err: Optional[torch.Tensor] = None,
+    check: bool = True, out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """``out[r] = sum_e weights[e] * table[cols[e]]`` over the entries of row r
+    of the CSR (rowptr int64 [n + 1], cols int32, ``weights`` fp32 or None = 1)
+    over the fp32 ``table`` [m, d], 1 <= d <= 512 (dr_csr_row_sum): fp32 or
+    bf16 [n, d] (``out_dtype``; bf16 is the fp32 sum rounded once). No atomics:
+    a row is summed in entry order in chunks of ``ROW_SUM_CHUNK`` entries whose
+    sums are added in chunk order, so it depends, bitwise, on its own entries
+    only. An empty row is exactly 0; a repeated column counts once per
+    occurrence. ``out`` (contiguous [n, d] of ``out_dtype``) is written in
+    place, every row of it, and returned. ``plan`` = ``row_sum_plan(rowptr)``, made once per CSR and
+    passed with the very ``rowptr`` it was made from: the call then reads
+    nothing back from the device (with ``check=False`` or a caller's ``err``).
+    Without a plan one is made here (one read-back). A cols entry outside
+    [0, m) adds nothing and is counted: with ``check`` and no ``err`` this call
+    reads the count (one sync) and raises IndexError; otherwise the count goes
+    to the caller's ``err`` (may be None), read when the caller chooses."""
+    dev = B.require_device(table, rowptr, cols, weights, err)
+    _need(table.dim() == 2 and table.dtype == torch.float32, "table must be fp32 2-D")
+    _contig(table, "table")
+    m, d = table.shape
+    _need(1 <= d <= ROW_SUM_MAX_D, f"table must have 1 to {ROW_SUM_MAX_D} columns")
+    _need(out_dtype in (torch.float32, torch.bfloat16), "out_dtype must be fp32 or bf16")
+    _need(cols.dtype == torch.int32 and cols.dim() == 1, "cols must be int32 1-D")
+    if weights is not None:
+        _need(weights.dtype == torch.float32 and weights.shape == cols.shape,
+              "weights must be fp32, one per entry of cols")
+        weights = weights.contiguous()
+    cols = cols.contiguous()
+    if plan is None:
+        plan = row_sum_plan(rowptr)
+    else:
+        _need(isinstance(plan, RowSumPlan) and rowptr.dtype == torch.int64
+              and rowptr.data_ptr() == plan.rowptr.data_ptr()
+              and rowptr.numel() == plan.n_rows + 1,
+              "plan must be row_sum_plan(rowptr) of this very rowptr tensor")
+    _need(plan.nnz == cols.numel(), "rowptr must rise from 0 to the number of entries of cols")
+    _need(plan.lists.device == dev, "plan and tensors on different devices")
+    n = plan.n_rows
+    if out is None:
+        out = torch.empty((n, d), dtype=out_dtype, device=dev)
+    else:
+        _need(out.dtype == out_dtype and out.shape == (n, d) and out.is_contiguous()
+              and out.device == dev, "out must be a contiguous [n, d] tensor of out_dtype")
+    if n == 0:
+        return out
+    ws = torch.empty((plan.n_chunks, d), dtype=torch.float32, device=dev) if plan.n_chunks else None
+    err, own = _counter(dev, err, check)
+    rc = B.lib().dr_csr_row_sum(
+        table.data_ptr() if m else None, m, d, plan.rowptr.data_ptr(),
+        cols.data_ptr() if cols.numel() else None, B.ptr(weights) if cols.numel() else None, n,
+        plan.lists.data_ptr(), plan.n_chunks, plan.n_long, out.data_ptr(), B.dtype_code(out_dtype),
+        B.ptr(ws), ws.numel() * 4 if ws is not None else 0, B.ptr(err), B.stream(dev),
+    )
+    _done(rc, "dr_csr_row_sum", own)
+    return out
+
+
+def csr_transpose(rowptr: torch.Tensor, cols: torch.Tensor, weights: Optional[torch.Tensor],
+                  n_cols: int) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """(rowptr_t int64 [n_cols + 1], cols_t int32, weights_t) of the transposed
+    CSR, on the same device (torch ops; the host works too). The entries are
+    ordered by a STABLE sort by column, so transposed row c lists its source
+    rows in ascending order (a repeated entry in its original order): the
+    fixed order ``csr_row_sum``'s reproducibility rests on. Every column must
+    lie in [0, n_cols) (ValueError; one read-back, once per CSR)."""
+    _need(rowptr.dtype == torch.int64 and rowptr.dim() == 1 and rowptr.numel() >= 1,
+          "rowptr int64 [n + 1]")
+    _need(cols.dtype == torch.int32 and cols.dim() == 1, "cols must be int32 1-D")
+    if weights is not None:
+        _need(weights.shape == cols.shape, "weights: one per entry of cols")
+    n, nnz, n_cols, dev = rowptr.numel() - 1, cols.numel(), int(n_cols), cols.device
+    _need(n_cols >= 0, "n_cols must be >= 0")
+    lens = rowptr[1:] - rowptr[:-1]
+    checks = [rowptr[0], rowptr[-1], (lens < 0).sum()]
+    if nnz:
+        checks += [cols.min().to(torch.int64), cols.max().to(torch.int64)]
+    got = torch.stack(checks).tolist()
+    _need(got[0] == 0 and got[1] == nnz and got[2] == 0,
+          "rowptr must rise from 0 to the number of entries of cols")
+    _need(not nnz or (got[3] >= 0 and got[4] < n_cols), "cols must lie in [0, n_cols)")
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), lens,
+                                   output_size=nnz)
+    order = torch.sort(cols, stable=True).indices
+    counts = torch.bincount(cols.to(torch.int64), minlength=n_cols)
+    rowptr_t = torch.zeros(n_cols + 1, dtype=torch.int64, device=dev)
+    rowptr_t[1:] = torch.cumsum(counts, 0)
+    return (rowptr_t, rows[order].to(torch.int32).contiguous(),
+            None if weights is None else weights[order].contiguous())
+
+
+class CsrMap:
+    """A row -> table-row map kept for a model's lifetime: the CSR (rowptr
+    int64 [n_rows + 1], cols int32, ``weights`` fp32 or None) over a table of
+    ``n_cols`` rows, its ``row_sum_plan`` and, made on first use and kept, the
+    transposed map ``.T`` with its own plan, which ``feature_sum``'s backward
+    sums over. Built from tensors on any device; ``to(device)`` moves it."""
+
+    def __init__(self, rowptr: torch.Tensor, cols: torch.Tensor,
+                 weights: Optional[torch.Tensor], n_cols: int, _transposed: "CsrMap" = None):
+        if weights is not None:
+            _need(weights.dtype == torch.float32, "weights must be fp32")
+        self.plan = row_sum_plan(rowptr)
+        self.rowptr, self.cols = self.plan.rowptr, cols.contiguous()
+        self.weights = None if weights is None else weights.contiguous()
+        self.n_rows, self.n_cols = self.plan.n_rows, int(n_cols)
+        _need(self.cols.dtype == torch.int32 and self.cols.dim() == 1
+              and self.cols.numel() == self.plan.nnz,
+              "cols must be int32 1-D, rowptr[-1] of them")
+        _need(self.weights is None or self.weights.shape == self.cols.shape,
+              "weights: one per entry of cols")
+        self._t = _transposed
+
+    @property
+    def T(self) -> "CsrMap":
+        if self._t is None:
+            rt, ct, wt = csr_transpose(self.rowptr, self.cols, self.weights, self.n_cols)
+            self._t = CsrMap(rt, ct, wt, self.n_rows, _transposed=self)
+        return self._t
+
+    def to(self, device) -> "CsrMap":
+        device = torch.device(device)
+        if self.rowptr.device == device:
+            return self
+        return CsrMap(self.rowptr.to(device), self.cols.to(device),
+                      None if self.weights is None else self.weights.to(device), self.n_cols)
+
+    def sum(self, table: torch.Tensor, out_dtype: torch.dtype = torch.float32,
+            err: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:
+        """``csr_row_sum`` of ``table`` [n_cols, d] over this map, with its plan."""
+        _need(table.dim() == 2 and table.size(0) == self.n_cols,
+              f"table must have the map's {self.n_cols} rows")
+        return csr_row_sum(table, self.rowptr, self.cols, self.weights, plan=self.plan,
+                           out_dtype=out_dtype, err=err, check=check)
+
+
+class _FeatureSum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, csr_map, checked):
+        ctx.csr_map = csr_map
+        return csr_map.sum(table, check=not checked)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        # d out[r] / d table[c] = sum of the weights of (r, c): the same sum
+        # over the transposed map; its columns are row numbers, valid by construction
+        grad = ctx.csr_map.T.sum(grad_out.to(torch.float32).contiguous(), check=False)
+        return grad, None, None
+
+
+def feature_sum(table: torch.Tensor, csr_map: CsrMap, checked: bool = False) -> torch.Tensor:
+    """``csr_map.sum(table)`` (fp32), differentiable in ``table`` only: the
+    backward is the same kernel over the transposed map, no atomics, bitwise
+    reproducible. ``checked``: the map's columns are known to lie in the table
+    (no read-back of the range counter)."""
+    return _FeatureSum.apply(table, csr_map, checked)

@@ -22,6 +22,13 @@ Same functions, arguments and return values as the reference. On the hot path:
   part as above, the regulariser's gradient by dr_ild_embedding_backward.
 * ``als_train_loop`` (not in the reference) trains a MatrixFactorization by
   implicit-feedback alternating least squares: two dr_als_solve per iteration.
+* FeatureMatrixFactorization (not in the reference) takes the one-launch
+  recommendation paths like MatrixFactorization (its composed tables are
+  scanned), and ``pair_wise_train_loop`` runs it with LogSigmoidDifferenceLoss
+  as a fused step: two dr_csr_row_sum compose the tables, one dr_bpr_fwd_bwd,
+  two transposed dr_csr_row_sum give the feature tables' gradients. The
+  point-wise loops run it through its forward and autograd;
+  ``diversity_pair_wise_train_loop`` and ``als_train_loop`` refuse it.
 """
 from __future__ import annotations
 
@@ -51,7 +58,7 @@ from divrec.losses import (
 from divrec.metrics import AUCScore
 from divrec.metrics import _rank
 from divrec.metrics.calibration_score import partition_labels
-from divrec.models import MatrixFactorization, RankingModel
+from divrec.models import FeatureMatrixFactorization, MatrixFactorization, RankingModel
 from divrec.models.matrix_factorization import MAX_RERANK_CANDIDATES, RERANKERS
 
 
@@ -182,6 +189,19 @@ def _mf_scoring(model: RankingModel) -> bool:
             and type(model).forward is MatrixFactorization.forward)
 
 
+def _feature_scoring(model: RankingModel) -> bool:
+    """The same for FeatureMatrixFactorization (a sibling of
+    MatrixFactorization, never a subclass: it has no ``user_embeddings``)."""
+    return (isinstance(model, FeatureMatrixFactorization)
+            and type(model).forward is FeatureMatrixFactorization.forward)
+
+
+def _table_scoring(model: RankingModel) -> bool:
+    """Models whose full-catalog scores are ONE scan of two tables
+    (``score_topk`` / ``recommend_diverse`` of the shared ``_TableModel``)."""
+    return _mf_scoring(model) or _feature_scoring(model)
+
+
 def _list_length(dataset: RankingDataset, excl, n_users: int, n_items: int, k: int) -> int:
     """Length of the reference's recommendation lists: min(k, candidates),
     where the candidates of a user are the catalog minus its frozen items.
@@ -209,11 +229,13 @@ def get_model_recommendations(dataset: RankingDataset, model: RankingModel,
                               number_of_recommendations: int) -> torch.LongTensor:
     """Top-``number_of_recommendations`` candidates of every user of
     ``dataset`` (LongTensor [U, k] on the CPU, like the reference), scored in
-    fp32 (MatrixFactorization.score_topk's faithful mode)."""
+    fp32 (MatrixFactorization.score_topk's faithful mode). A
+    FeatureMatrixFactorization takes the same one-launch path over its
+    composed tables; any other model the per-user loop."""
     k = int(number_of_recommendations)
     n_users = int(dataset.data.number_of_users)
     n_items = int(dataset.data.number_of_items)
-    if _mf_scoring(model) and n_users <= model.no_users and n_items <= model.no_items:
+    if _table_scoring(model) and n_users <= model.no_users and n_items <= model.no_items:
         if n_users == 0:
             return torch.LongTensor([])
         excl = dataset.exclusion_csr()
@@ -251,6 +273,7 @@ def get_diverse_recommendations(dataset: RankingDataset, model: RankingModel,
     ``dataset.data.item_features[items_partition_feature]`` (at most 64 of
     them), the user's profile the label histogram of its ``frozen`` items, its
     history (``ops.label_profile`` over ``dataset.exclusion_csr()``).
+    A FeatureMatrixFactorization is served like a MatrixFactorization.
     ValueError for a model outside the MF fast path, for ragged candidate
     lists (as ``get_model_recommendations``), for a list that ends early
     (fewer eligible candidates than picks) and, for "calibrated", without
@@ -263,7 +286,7 @@ def get_diverse_recommendations(dataset: RankingDataset, model: RankingModel,
                          f"{MAX_RERANK_CANDIDATES}, got {k} and {cands}")
     n_users = int(dataset.data.number_of_users)
     n_items = int(dataset.data.number_of_items)
-    if not (_mf_scoring(model) and n_users <= model.no_users and n_items <= model.no_items):
+    if not (_table_scoring(model) and n_users <= model.no_users and n_items <= model.no_items):
         raise ValueError("get_diverse_recommendations needs a MatrixFactorization model (its own "
                          "forward) that covers the dataset's users and items")
     if n_users == 0:
@@ -457,6 +480,62 @@ def _bpr_fast_path(model, loss, scores) -> bool:
             and (scores is None or all(type(s) is AUCScore for s in scores)))
 
 
+def _feature_bpr_fast_path(model, loss, scores) -> bool:
+    return (_feature_scoring(model) and type(loss) is LogSigmoidDifferenceLoss
+            and (scores is None or all(type(s) is AUCScore for s in scores)))
+
+
+def _composed_grads(model: FeatureMatrixFactorization, U: torch.Tensor, I: torch.Tensor):
+    """The two dense composed-gradient buffers of the fused feature step
+    ([no_users, d] and [no_items, d] fp32): kept on the model, zeroed per batch."""
+    bufs = getattr(model, "_composed_grad_buffers", None)
+    if (bufs is None or bufs[0].shape != U.shape or bufs[1].shape != I.shape
+            or bufs[0].device != U.device):
+        bufs = (torch.empty_like(U), torch.empty_like(I))
+        model._composed_grad_buffers = bufs
+    bufs[0].zero_(), bufs[1].zero_()
+    return bufs
+
+
+def _feature_pair_wise_batch(model: FeatureMatrixFactorization, scores, batch, epoch_err):
+    """One batch of the fused FeatureMatrixFactorization + BPR step, up to the
+    optimizer step: (1) compose both tables WHOLE (two dr_csr_row_sum), like
+    the reference's dense Adam over whole tables; (2) ONE dr_bpr_fwd_bwd over
+    the composed tables into the two composed-gradient buffers; (3) two
+    dr_csr_row_sum over the transposed maps into the feature tables' ``.grad``
+    (no atomics: given the composed gradients, bitwise reproducible).
+    Bytes per step beyond dr_bpr_fwd_bwd's own, with nnz the maps' entries, R
+    = no_users + no_items rows and F = Fu + Fi features, all times 4 d:
+    compose reads nnz and writes R; the buffers' zeroing writes R; the
+    transposed sums read nnz and write F; so 2 nnz + 2 R + F rows of d floats,
+    whatever the batch touches (a row-subset compose is out of scope).
+    Returns what ``_pair_wise_batch`` returns."""
+    user_id, pos, neg, _, _, _ = batch
+    dev = model._device()
+    host = user_id.device.type == "cpu"
+    if host:  # host batches: raise before any compute
+        _backend.host_ids_in_range(user_id, model.no_users, "user_id")
+        _backend.host_ids_in_range(pos, model.no_items, "positive item_id")
+        _backend.host_ids_in_range(neg, model.no_items, "negative item_id")
+    ids = tuple(t.to(dev, torch.int64, non_blocking=True) for t in (user_id, pos, neg))
+    if not host:
+        _device_ids_in_range(ids[0], model.no_users, ids[1:], model.no_items)
+    Wu, Wi = model.user_feature_embeddings.weight, model.item_feature_embeddings.weight
+    with torch.no_grad():
+        U, I = model._tables()
+        gU, gI = _composed_grads(model, U, I)
+        epoch_err = _epoch_counter(epoch_err, dev)
+        B = ids[0].numel()
+        losses_b, hits = ops.bpr_fwd_bwd(U, I, *ids, 1.0 / B, gU, gI, err=epoch_err, check=False)
+        user_map, item_map = model._maps(dev)
+        for W, g, m in ((Wu, gU, user_map), (Wi, gI, item_map)):
+            grad = m.T.sum(g, check=False)  # columns of a transpose: row numbers, valid
+            W.grad = grad if W.grad is None else W.grad.add_(grad)
+    loss_value = torch.sum(losses_b, dim=0) / B
+    row = [s.reduce_loss_values(hits).double() for s in scores or ()]
+    return ids, loss_value.detach(), torch.stack(row) if row else None, epoch_err
+
+
 def _pair_wise_batch(model: RankingModel, loss: PairWiseLoss, scores, fused: bool, batch,
                      epoch_err):
     """One batch's pairwise part, up to the optimizer step (not taken here):
@@ -501,18 +580,36 @@ def pair_wise_train_loop(dataset: PairWiseDataset, model: RankingModel, loss: Pa
                          optimizer: torch.optim.Optimizer,
                          scores: Optional[List[PairWiseLoss]] = None,
                          **loader_params) -> Tuple[float, List[float]]:
-    """One epoch of pairwise training; returns (mean batch loss, [mean score])."""
+    """One epoch of pairwise training; returns (mean batch loss, [mean score]).
+
+    A FeatureMatrixFactorization with LogSigmoidDifferenceLoss (+ AUCScore
+    scores) runs the fused step of ``_feature_pair_wise_batch`` (its docstring
+    prices it), then dr_adam_dense for a plain Adam or the optimizer's own
+    step; with other losses it trains through its forward and autograd. The
+    lazy SparseAdam path is not offered for it (ValueError): a feature row's
+    gradient gathers every row that holds the feature, so no small set of
+    touched rows exists."""
     assert scores is None or all(score.reduce for score in scores)
+    if isinstance(model, FeatureMatrixFactorization) and isinstance(optimizer,
+                                                                    torch.optim.SparseAdam):
+        raise ValueError("pair_wise_train_loop: FeatureMatrixFactorization has dense gradients "
+                         "(a feature gathers every row that holds it); the lazy SparseAdam path "
+                         "is not offered for it, use torch.optim.Adam")
     model.train()
     n_scores = len(scores) if scores is not None else 0
     batch_losses, batch_scores = [], []
+    featured = _feature_bpr_fast_path(model, loss, scores)
     fused = _bpr_fast_path(model, loss, scores)
-    adam = fused and _plain_adam(optimizer)  # the generic path steps the optimizer itself
+    adam = (fused or featured) and _plain_adam(optimizer)  # the generic path steps the optimizer itself
     lazy = fused and _plain_sparse_adam(optimizer)
     epoch_err = None  # id range errors of the fused kernel on device batches
     for batch in dataset.loader(**loader_params):
-        ids, loss_value, row, epoch_err = _pair_wise_batch(model, loss, scores, fused, batch,
-                                                           epoch_err)
+        if featured:
+            ids, loss_value, row, epoch_err = _feature_pair_wise_batch(model, scores, batch,
+                                                                       epoch_err)
+        else:
+            ids, loss_value, row, epoch_err = _pair_wise_batch(model, loss, scores, fused, batch,
+                                                               epoch_err)
         _optimizer_step(optimizer, adam, lazy, lambda: {
             model.user_embeddings.weight: torch.unique(ids[0]),
             model.item_embeddings.weight: torch.unique(torch.cat(ids[1:]))})

@@ -524,6 +524,70 @@ int dr_als_solve(const float* fixed_table, int64_t n_fixed_rows, int d, const fl
                  const int64_t* rowptr, const int32_t* cols, const float* weights, int64_t n_rows,
                  float alpha, float reg, float* out, uint32_t* err, dr_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Weighted CSR row sum over an embedding table (no reference symbol): the
+ * composition of a table from feature embeddings (a LightFM-style hybrid:
+ * a row's embedding is the weighted sum of its features' embeddings) and,
+ * over the transposed CSR, its exact gradient with respect to the feature
+ * table. table fp32 [n_table_rows, d]; the rows to sum are a CSR over it
+ * (rowptr int64 [n_rows + 1], cols int32 [nnz], weights fp32 [nnz] or NULL =
+ * all 1):
+ *   out[r, :] = sum_{e in [rowptr[r], rowptr[r + 1])} w[e] * table[cols[e], :]
+ * out is [n_rows, d], out_dtype DR_F32 or DR_BF16; the bf16 form is the fp32
+ * sum rounded once to nearest-even.
+ * Order of the sum: a row's entries are cut into chunks of DR_ROW_SUM_CHUNK
+ * (= L) consecutive entries; a chunk is summed from 0 in entry order by fp32
+ * FMAs, and a row's chunk sums are added in chunk order. No atomics touch the
+ * result: a row depends, bitwise, on its own entry list and on L only,
+ * whatever the grid, the CU count, its place in the CSR, its neighbours, or
+ * whether a plan is given.
+ * The plan (optional; it decides who sums, never what): with plan = NULL, or
+ * n_long = 0, the lane groups stride over the rows and one group sums a whole
+ * row, however long. The plan of a CSR with rows longer than L lists EVERY
+ * work item, longest first (a stable sort): each of a long row's chunks, whose
+ * sum goes to a partial row of the workspace (fp32 [n_chunks, d],
+ * dr_csr_row_sum_workspace bytes), and each other row whole. The groups take
+ * the items in serpentine order, so their loads stay equal however skewed the
+ * rows are, and a second kernel (one workgroup per long row) adds each long
+ * row's partial rows in chunk order: a CSR with a few very long rows (the
+ * transpose of a map with popular features) then costs about what an evenly
+ * filled one does. With n_items = n_rows - n_long + n_chunks, plan is int64
+ * [3 * n_items + 2 * n_long + 1] on the device, five lists one after the
+ * other:
+ *   item_row  [n_items]     the row of item i
+ *   item_beg  [n_items]     its first entry, an index into cols: the item
+ *                           covers at most L entries from there, to the
+ *                           row's end at the latest
+ *   item_slot [n_items]     the partial row its sum goes to, or -1: the item
+ *                           is a whole row and goes to out
+ *   long_row  [n_long]      the rows longer than L
+ *   long_first[n_long + 1]  long row j owns the partial rows long_first[j] ..
+ *                           long_first[j + 1], its chunks in order
+ * A row that a given plan does not cover is not written (or not wholly
+ * summed); an index outside its range is skipped, never followed: a wrong
+ * plan gives wrong sums, never an access outside the arrays.
+ * An empty row WRITES zeros. A cols entry outside [0, n_table_rows) adds
+ * nothing and is added to *err (a 32-bit device counter, may be NULL). A
+ * repeated column counts once per occurrence. rowptr must be non-decreasing
+ * with rowptr[n_rows] = nnz (the caller's to check; the kernel reads
+ * cols[rowptr[r] .. rowptr[r + 1])). 1 <= d <= DR_ROW_SUM_MAX_D,
+ * n_table_rows in [0, 2^31), 0 <= 2 n_long <= n_chunks; cols may be NULL when
+ * every row is empty, table when n_table_rows = 0. n_rows = 0 is a no-op.
+ * Launch: lane groups of 4 .. 64 lanes, 16 B of a row per lane (d a multiple
+ * of 4 and 16-B aligned pointers; one float per lane otherwise), several
+ * entries' rows in flight per group; a persistent grid of as many 256-thread
+ * workgroups per CU as are resident (DR_KNOB_SCAN_SLOTS caps the CUs, as for
+ * dr_als_solve). No host synchronisation. */
+#define DR_ROW_SUM_CHUNK 512
+#define DR_ROW_SUM_MAX_D 512
+int dr_csr_row_sum_chunk(void); /* DR_ROW_SUM_CHUNK of the built library */
+size_t dr_csr_row_sum_workspace(int64_t n_chunks, int d);
+int dr_csr_row_sum(const float* table, int64_t n_table_rows, int d, const int64_t* rowptr,
+                   const int32_t* cols, const float* weights, int64_t n_rows,
+                   const int64_t* plan, int64_t n_chunks, int64_t n_long, void* out,
+                   int out_dtype, void* workspace, size_t workspace_bytes, uint32_t* err,
+                   dr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
