@@ -261,18 +261,6 @@ __global__ __launch_bounds__(kThreads) void als_solve_kernel(
   if (nbad && err) atomicAdd(err, nbad);
 }
 
-// Persistent grid: as many workgroups per CU as are resident at once (the
-// kernel's own occupancy; 1 if the query fails) over dr::persistent_cus() CUs.
-template <typename Kernel>
-dim3 row_grid(Kernel kernel, int64_t n_rows) {
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, 0) != hipSuccess ||
-      per_cu < 1)
-    per_cu = 1;
-  const int64_t cap = (int64_t)dr::persistent_cus() * per_cu;
-  return dim3((unsigned)(n_rows < cap ? n_rows : cap));
-}
-
 }  // namespace
 
 extern "C" int dr_als_solve(const float* fixed_table, int64_t n_fixed_rows, int d,
@@ -289,7 +277,8 @@ extern "C" int dr_als_solve(const float* fixed_table, int64_t n_fixed_rows, int 
   DR_CHECK_ARG((fixed_table || n_fixed_rows == 0) && gram && rowptr && out, "null pointer");
   hipStream_t s = (hipStream_t)stream;
 #define DR_ALS(DD)                                                                              \
-  hipLaunchKernelGGL(als_solve_kernel<DD>, row_grid(als_solve_kernel<DD>, n_rows),               \
+  hipLaunchKernelGGL(als_solve_kernel<DD>,                                                      \
+                     dr::persistent_grid(als_solve_kernel<DD>, kThreads, n_rows, 1),             \
                      dim3(kThreads), 0, s, fixed_table, n_fixed_rows, gram, rowptr, cols,        \
                      weights, n_rows, alpha, reg, out, err)
   if (d == 32) DR_ALS(32); else if (d == 64) DR_ALS(64); else DR_ALS(128);

@@ -163,6 +163,35 @@ __global__ __launch_bounds__(kThreads) void calib_pick_kernel(
   }
 }
 
+// A wave's label histogram of the ids id(i), i = first + lane, + 64, ... < end,
+// in its LDS row hist[kMaxG]: n is this lane's category's count,
+// total the count of all labelled ids (every lane). An id or a label out of
+// range is counted into *err; a negative id too where NEG_IS_BAD (a history
+// has no empty slots), elsewhere it is an empty slot. The caller syncs the
+// wave (wave_lds_sync) before its next call.
+struct LabelCount { int n, total; };
+template <bool NEG_IS_BAD, typename Idx, typename IdAt>
+__device__ __forceinline__ LabelCount label_histogram(int* hist, int lane, Idx first, Idx end,
+                                                      IdAt id, const int32_t* labels,
+                                                      int64_t n_items, int G, int32_t* err) {
+  hist[lane] = 0;
+  dr::wave_lds_sync();
+  int nbad = 0;
+  for (Idx i = first + lane; i < end; i += 64) {
+    const auto it = id(i);
+    const int lab = label_of(it, labels, n_items, G, nbad);
+    if (NEG_IS_BAD && it < 0) ++nbad;
+    if (lab >= 0) atomicAdd(&hist[lab], 1);
+  }
+  if (nbad && err) atomicAdd(err, nbad);
+  dr::wave_lds_sync();
+  const int n = hist[lane];
+  int total = n;
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) total += __shfl_xor(total, m);
+  return {n, total};
+}
+
 // One wave per CSR row: labels of the row's items counted into the wave's LDS
 // histogram, then out[row, g] = n_g / total (one fp32 divide of two integers).
 __global__ __launch_bounds__(kThreads) void label_profile_kernel(
@@ -173,23 +202,10 @@ __global__ __launch_bounds__(kThreads) void label_profile_kernel(
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t n_waves = (int64_t)gridDim.x * kWaves;
   for (int64_t r = (int64_t)blockIdx.x * kWaves + w; r < n_rows; r += n_waves) {
-    s_hist[w][lane] = 0;
-    dr::wave_lds_sync();
-    int nbad = 0;
-    const int64_t end = rowptr[r + 1];
-    for (int64_t i = rowptr[r] + lane; i < end; i += 64) {
-      const int32_t it = items[i];
-      const int lab = label_of(it, labels, n_items, G, nbad);
-      if (it < 0) ++nbad;  // a history has no empty slots: a negative id is a bad id
-      if (lab >= 0) atomicAdd(&s_hist[w][lab], 1);
-    }
-    if (nbad && err) atomicAdd(err, nbad);
-    dr::wave_lds_sync();
-    const int n = s_hist[w][lane];
-    int total = n;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) total += __shfl_xor(total, m);
-    if (lane < G) out[r * G + lane] = total > 0 ? (float)n / (float)total : 0.f;
+    const LabelCount c = label_histogram<true>(
+        s_hist[w], lane, rowptr[r], rowptr[r + 1], [&](int64_t i) { return items[i]; }, labels,
+        n_items, G, err);
+    if (lane < G) out[r * G + lane] = c.total > 0 ? (float)c.n / (float)c.total : 0.f;
     dr::wave_lds_sync();
   }
 }
@@ -205,41 +221,22 @@ __global__ __launch_bounds__(kThreads) void calibration_kl_kernel(
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t n_waves = (int64_t)gridDim.x * kWaves;
   for (int64_t u = (int64_t)blockIdx.x * kWaves + w; u < n_users; u += n_waves) {
-    s_hist[w][lane] = 0;
-    dr::wave_lds_sync();
-    int nbad = 0;
-    for (int i = lane; i < k; i += 64) {
-      const int lab = label_of((int64_t)recs[u * k + i], labels, n_items, G, nbad);
-      if (lab >= 0) atomicAdd(&s_hist[w][lab], 1);
-    }
-    if (nbad && err) atomicAdd(err, nbad);
-    dr::wave_lds_sync();
-    const int n = s_hist[w][lane];
-    int total = n;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) total += __shfl_xor(total, m);
+    const LabelCount c = label_histogram<false>(
+        s_hist[w], lane, 0, k, [&](int i) { return recs[u * k + i]; }, labels, n_items, G, err);
     const float p = profile_entry(profile + u * G, G, lane);
     const float logp = p > 0.f ? logf(p) : 0.f;
-    const float inv = total > 0 ? 1.f / (float)total : 0.f;
-    const float kl = dr::wave_sum_dpp_f32(kl_term(p, logp, (float)n * inv));
+    const float inv = c.total > 0 ? 1.f / (float)c.total : 0.f;
+    const float kl = dr::wave_sum_dpp_f32(kl_term(p, logp, (float)c.n * inv));
     if (lane == 0) out[u] = kl;
     dr::wave_lds_sync();
   }
 }
 
-// Persistent grid of one-wave workers: as many workgroups per CU as are
-// resident at once (the kernel's own occupancy; 4 if the query fails), each
-// wave looping over the units (users, rows). The CUs planned for are
-// dr::persistent_cus(), so the DR_KNOB_SCAN_SLOTS cap applies as for
-// dr_mmr_rerank and tests reach many users per wave with few users.
+// dr::persistent_grid of one-wave workers, each wave looping over the units
+// (users, rows); 4 workgroups per CU if the occupancy query fails.
 template <typename Kernel>
 dim3 wave_grid(Kernel kernel, int64_t units) {
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, 0) != hipSuccess ||
-      per_cu < 1)
-    per_cu = 4;
-  const int64_t need = dr::ceil_div(units, kWaves), cap = (int64_t)dr::persistent_cus() * per_cu;
-  return dim3((unsigned)(need < cap ? need : cap));
+  return dr::persistent_grid(kernel, kThreads, dr::ceil_div(units, kWaves), 4);
 }
 
 // The label-table arguments the three calls share.

@@ -60,8 +60,20 @@ constexpr int kWave = 64;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
-__device__ __forceinline__ float bf16_bits_to_f32(uint32_t b16) {
-  return __uint_as_float(b16 << 16);
+// The two bf16 values of a packed word as fp32: element 0 (low half), element 1.
+__device__ __forceinline__ float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+
+// Is `item` in the ascending list[0, n)? N is the count's type and T the type
+// the comparison is made in (an int64 id is searched without narrowing).
+template <typename N, typename T>
+__device__ __forceinline__ bool sorted_contains(const int32_t* __restrict__ list, N n, T item) {
+  N lo = 0, hi = n;
+  while (lo < hi) {
+    const N mid = (lo + hi) >> 1;
+    if ((T)list[mid] < item) lo = mid + 1; else hi = mid;
+  }
+  return lo < n && (T)list[lo] == item;
 }
 
 // LDS written by the lanes of a wave is visible to its other lanes after this
@@ -188,6 +200,15 @@ __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int lane) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+// Three wave sums, three summation orders (their results may differ in the
+// last bit, so one does not stand in for another):
+//   wave_sum_f32      the shuffle sum: six ds_bpermute round trips, every lane
+//                     gets the sum;
+//   wave_sum_dpp_f32  the uniform DPP sum (below): row_bcast steps carry the
+//                     result into lane 63, which is read back wave-uniform;
+//   wave_allsum_f32   the all-lanes sum (below): DPP rotations and
+//                     v_permlane16/32_swap, VALU only, every lane gets the sum;
+//                     half_sum_f32 is its 32-lane part.
 __device__ __forceinline__ float wave_sum_f32(float v) {
 #pragma unroll
   for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
@@ -259,6 +280,70 @@ __device__ __forceinline__ float wave_sum_dpp_f32(float v) {  // uniform: the wa
   v += dpp_f32<0x143, 0xC>(v);
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
+// v[lane] and v[lane ^ 16] / v[lane ^ 32], in an order that depends on the
+// lane's half (v_permlane16/32_swap: one VALU, no LDS round trip): for
+// commutative merges.
+struct F32Pair { float a, b; };
+__device__ __forceinline__ F32Pair swap16_f32(float v) {
+  const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return {__uint_as_float(p[0]), __uint_as_float(p[1])};
+}
+__device__ __forceinline__ F32Pair swap32_f32(float v) {
+  const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return {__uint_as_float(p[0]), __uint_as_float(p[1])};
+}
+// The two 16-lane rows of a 32-lane group added.
+__device__ __forceinline__ float add_rows_f32(float v) {
+  const F32Pair p = swap16_f32(v);
+  return p.a + p.b;
+}
+// Sum over a 32-lane group in VALU only; every lane of the group gets it. Both
+// groups of a wave may call it under different exec masks: no step crosses
+// the group.
+__device__ __forceinline__ float half_sum_f32(float v) {
+  v = quad_sum_f32(v);
+  v += dpp_f32<0x124>(v);  // row_ror:4
+  v += dpp_f32<0x128>(v);  // row_ror:8
+  return add_rows_f32(v);
+}
+__device__ __forceinline__ float wave_allsum_f32(float v) {  // every lane: the wave's sum
+  const F32Pair p = swap32_f32(half_sum_f32(v));
+  return p.a + p.b;
+}
+
+// ---------------------------------------------------------------- VMEM waits
+// s_waitcnt vmcnt(N) only (expcnt / lgkmcnt left at their maxima): what every
+// user of the LDS-DMA below waits with.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N < 64, "vmcnt range");
+  __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (0x7 << 4) | (0xF << 8));
+}
+// Two waits for a wave-uniform run-time count n. wait_vmcnt_dyn rounds n down
+// to a power of two (waits for a little more than required, always correct):
+// six scalar compares, for a wait at every stage of a long loop.
+// wait_vm_exact<LO, HI> waits for exactly n in [LO, HI] (a binary search over
+// the immediates, six scalar branches), for a pipeline whose younger loads
+// must stay in flight.
+__device__ __forceinline__ void wait_vmcnt_dyn(int n) {
+  if (n >= 32) wait_vmcnt<32>();
+  else if (n >= 16) wait_vmcnt<16>();
+  else if (n >= 8) wait_vmcnt<8>();
+  else if (n >= 4) wait_vmcnt<4>();
+  else if (n >= 2) wait_vmcnt<2>();
+  else if (n >= 1) wait_vmcnt<1>();
+  else wait_vmcnt<0>();
+}
+template <int LO, int HI>
+__device__ __forceinline__ void wait_vm_exact(int n) {
+  if constexpr (LO == HI) {
+    asm volatile("s_waitcnt vmcnt(%c0)" : : "i"(LO) : "memory");
+  } else {
+    constexpr int MID = (LO + HI) / 2;
+    if (n <= MID) wait_vm_exact<LO, MID>(n);
+    else wait_vm_exact<MID + 1, HI>(n);
+  }
+}
 
 // ---------------------------------------------------------------- LDS-DMA
 // global_load_lds_*: a wave's 64 dwords (or 16-B chunks) go from global memory
@@ -294,5 +379,20 @@ __device__ __forceinline__ void lds_dma_b128(const char* base, uint32_t off, uin
 #pragma clang diagnostic pop
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Grid of a persistent kernel whose workgroups loop over the work: as many
+// workgroups per CU as are resident at once (the kernel's own occupancy;
+// fallback_per_cu if the query fails) over persistent_cus() CUs, and no more
+// than the work needs. The DR_KNOB_SCAN_SLOTS cap applies through
+// persistent_cus(), so tests reach many units per workgroup with little work.
+template <typename Kernel>
+dim3 persistent_grid(Kernel kernel, int threads, int64_t blocks_needed, int fallback_per_cu) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess ||
+      per_cu < 1)
+    per_cu = fallback_per_cu;
+  const int64_t cap = (int64_t)persistent_cus() * per_cu;
+  return dim3((unsigned)(blocks_needed < cap ? blocks_needed : cap));
+}
 
 }  // namespace dr

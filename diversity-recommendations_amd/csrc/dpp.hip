@@ -37,12 +37,11 @@ constexpr int kMaxK = 128;               // picks (basis rows) per user
 using dr::bf16x8;
 using dr::f32x4;
 
-// the DPP wave reductions of common.h
+// the bf16 unpacking and the DPP wave reductions of common.h
+using dr::bf16_hi;
+using dr::bf16_lo;
 using dr::quad_sum_f32;
 using dr::wave_max_u64;
-
-__device__ __forceinline__ float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
 // sum of squares of 8 bf16 (one 16-B chunk of a row), even and odd elements apart
 __device__ __forceinline__ void sumsq8(const uint4 u, float& even, float& odd) {

@@ -265,36 +265,23 @@ __global__ __launch_bounds__(kThreads) void row_sum_combine_kernel(
   }
 }
 
-// Persistent grid: as many workgroups per CU as are resident at once (the
-// kernel's own occupancy; 1 if the query fails) over dr::persistent_cus() CUs,
-// and no more than the work needs.
-template <typename Kernel>
-dim3 capped_grid(Kernel kernel, int64_t blocks_needed) {
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, 0) != hipSuccess ||
-      per_cu < 1)
-    per_cu = 1;
-  const int64_t cap = (int64_t)dr::persistent_cus() * per_cu;
-  return dim3((unsigned)(blocks_needed < cap ? blocks_needed : cap));
-}
-
 template <int G, int NV, typename V, int U>
 int launch(const float* table, int64_t n_table_rows, int dv, const int64_t* rowptr,
            const int32_t* cols, const float* weights, int64_t n_rows, const RowSumPlan& plan,
            int64_t n_items, int64_t n_chunks, int64_t n_long, void* workspace, void* out,
            bool out_bf16, uint32_t* err, hipStream_t s) {
   auto sum = row_sum_kernel<G, NV, V, U>;
-  const int64_t work = n_items ? n_items : n_rows;
-  hipLaunchKernelGGL(sum, capped_grid(sum, dr::ceil_div(work, kThreads / G)), dim3(kThreads), 0, s,
+  const int64_t blocks = dr::ceil_div(n_items ? n_items : n_rows, kThreads / G);
+  hipLaunchKernelGGL(sum, dr::persistent_grid(sum, kThreads, blocks, 1), dim3(kThreads), 0, s,
                      reinterpret_cast<const V*>(table), n_table_rows, dv, rowptr, cols, weights,
                      n_rows, plan, n_items, n_chunks, reinterpret_cast<V*>(workspace), out,
                      out_bf16, err);
   DR_CHECK_LAUNCH();
   if (n_long) {
     auto combine = row_sum_combine_kernel<V>;
-    hipLaunchKernelGGL(combine, capped_grid(combine, n_long), dim3(kThreads), 0, s,
-                       reinterpret_cast<const V*>(workspace), dv, plan, n_long, n_chunks, n_rows,
-                       out, out_bf16);
+    hipLaunchKernelGGL(combine, dr::persistent_grid(combine, kThreads, n_long, 1), dim3(kThreads),
+                       0, s, reinterpret_cast<const V*>(workspace), dv, plan, n_long, n_chunks,
+                       n_rows, out, out_bf16);
     DR_CHECK_LAUNCH();
   }
   return DR_OK;

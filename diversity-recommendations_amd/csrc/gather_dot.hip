@@ -44,8 +44,8 @@ struct Vec16<__bf16> {
     const uint32_t wa[4] = {a.x, a.y, a.z, a.w}, wb[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      s = fmaf(dr::bf16_bits_to_f32(wa[i] & 0xffffu), dr::bf16_bits_to_f32(wb[i] & 0xffffu), s);
-      s = fmaf(dr::bf16_bits_to_f32(wa[i] >> 16), dr::bf16_bits_to_f32(wb[i] >> 16), s);
+      s = fmaf(dr::bf16_lo(wa[i]), dr::bf16_lo(wb[i]), s);
+      s = fmaf(dr::bf16_hi(wa[i]), dr::bf16_hi(wb[i]), s);
     }
     return s;
   }

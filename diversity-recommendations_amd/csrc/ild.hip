@@ -523,7 +523,7 @@ bool launch_regs(const R* recs, int64_t n_users, int k, const __bf16* E, int64_t
 //     the epilogue is one FMA per Gram element (below).
 // Row buffers per wave (NB) as many as fit the 160-KB LDS, at most 16:
 // k = 100, d = 128 keeps one user per wave in flight (4 x 25 KB per CU),
-// k = 10 nine.
+// k = 10 twelve.
 #ifdef DR_ILD_DIAG
 // per-wave s_memtime cycles of each phase (diag builds only): wait, LDS
 // reads, issue + compute, tail, total, users
@@ -561,37 +561,6 @@ inline StreamShape stream_shape(int k, int d, int rec_bytes) {
   double v;
   if (dr::plan_knob(DR_KNOB_ILD_BUFS, &v) && (int)v < sh.nb) sh.nb = (int)v;  // A/B knob
   return sh;
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform n in [LO, HI] (an immediate: binary
-// search over the encodings, six scalar branches)
-template <int LO, int HI>
-__device__ __forceinline__ void wait_vm_exact(int n) {
-  if constexpr (LO == HI) {
-    asm volatile("s_waitcnt vmcnt(%c0)" : : "i"(LO) : "memory");
-  } else {
-    constexpr int MID = (LO + HI) / 2;
-    if (n <= MID) wait_vm_exact<LO, MID>(n);
-    else wait_vm_exact<MID + 1, HI>(n);
-  }
-}
-
-// Sum over the wave in VALU only (the __shfl_xor form is six dependent LDS
-// round trips, ds_bpermute): quad and row rotations by DPP, then the 16- and
-// 32-lane halves by v_permlane16/32_swap. Every lane gets the sum.
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-  auto dpp = [](float x, auto CTRL) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(CTRL)::value,
-                                                      0xf, 0xf, false));
-  };
-  v += dpp(v, std::integral_constant<int, 0xB1>{});   // quad_perm [1,0,3,2]
-  v += dpp(v, std::integral_constant<int, 0x4E>{});   // quad_perm [2,3,0,1]
-  v += dpp(v, std::integral_constant<int, 0x124>{});  // row_ror:4
-  v += dpp(v, std::integral_constant<int, 0x128>{});  // row_ror:8
-  const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(p[0]) + __uint_as_float(p[1]);
-  const auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
 }
 
 template <typename R, int D, int NT, int KIND>
@@ -698,7 +667,7 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
     // of user n + nb) have landed; only younger ops may be pending
     const int vm = n < nb ? (nb - 1 - n) * (per - 1) + n * per : 1 + (nb - 1) * per;
     ILD_T0(t_w);
-    wait_vm_exact<0, 63>(vm);
+    dr::wait_vm_exact<0, 63>(vm);
     ILD_ADD(0, t_w);
     ILD_T0(t_f);
     // one batch of LDS reads: the user's fragments, the next user's piece ids
@@ -780,7 +749,7 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
           sum = fmaf(wj, c.x + c.y, sum);
         }
       }
-      sum = wave_sum_dpp(sum);
+      sum = dr::wave_allsum_f32(sum);
       if constexpr (KIND == DR_ILD_COSINE) sum = (float)(k * (k - 1) / 2) - sum;
     } else {
       // |e_i - e_j| = sqrt(|e_i|^2 + |e_j|^2 - 2 G_ij): one sqrt per pair
@@ -798,7 +767,7 @@ __global__ __launch_bounds__(kStreamWaves * 64, 1) void ild_embedding_stream(
             sum += pair_term<KIND>(q, g, wi, w[j], jv, ti < tj, 32 * ti, j, h);
         }
       }
-      sum = wave_sum_dpp(sum);
+      sum = dr::wave_allsum_f32(sum);
     }
     float res = sum / (float)(k * (k - 1));
 #ifdef DR_ILD_DIAG

@@ -36,40 +36,23 @@ constexpr int kGroups = kBlock / 32;
 constexpr int kGradMaxK = 128;
 constexpr int kGradMaxD = 256;
 
-// A DPP move inside the 16-lane row: CTRL 0x00-0xFF quad_perm, 0x121-0x12F row_ror.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
-}
-// The two 16-lane rows of a 32-lane group added (v_permlane16_swap).
-__device__ __forceinline__ float add_rows(float v) {
-  const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(p[0]) + __uint_as_float(p[1]);
-}
-// Sum over a 32-lane group in VALU only (DPP quad and row rotations, then the
-// two rows); every lane of the group gets it. Both groups of a wave may call
-// it under different exec masks: no step crosses the group.
-__device__ __forceinline__ float group_sum(float v) {
-  v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_mov<0x124>(v);  // row_ror:4
-  v += dpp_mov<0x128>(v);  // row_ror:8
-  return add_rows(v);
-}
-// Four sums at once: lane l of the group gets the group's sum of v[l & 3].
+using dr::dpp_f32;  // CTRL 0x00-0xFF quad_perm, 0x121-0x12F row_ror: inside the 16-lane row
+
+// dr::half_sum_f32 for four sums at once: lane l of the group gets the group's
+// sum of v[l & 3].
 // Inside the quad each exchange halves the values a lane carries (after the
 // lane ^ 1 step it keeps j = b and b + 2, b = l & 1; after the lane ^ 2 step
 // j = l & 3); the rotations by 4 and 8 and the row swap keep l & 3.
 __device__ __forceinline__ float group_sum4(const float (&v)[4], int gl) {
   const bool b = gl & 1, c = gl & 2;
-  const float t0 = v[0] + dpp_mov<0xB1>(v[0]), t1 = v[1] + dpp_mov<0xB1>(v[1]);
-  const float t2 = v[2] + dpp_mov<0xB1>(v[2]), t3 = v[3] + dpp_mov<0xB1>(v[3]);
+  const float t0 = v[0] + dpp_f32<0xB1>(v[0]), t1 = v[1] + dpp_f32<0xB1>(v[1]);
+  const float t2 = v[2] + dpp_f32<0xB1>(v[2]), t3 = v[3] + dpp_f32<0xB1>(v[3]);
   const float a0 = b ? t1 : t0, a1 = b ? t3 : t2;
-  const float u0 = a0 + dpp_mov<0x4E>(a0), u1 = a1 + dpp_mov<0x4E>(a1);
+  const float u0 = a0 + dpp_f32<0x4E>(a0), u1 = a1 + dpp_f32<0x4E>(a1);
   float r = c ? u1 : u0;
-  r += dpp_mov<0x124>(r);
-  r += dpp_mov<0x128>(r);
-  return add_rows(r);
+  r += dpp_f32<0x124>(r);
+  r += dpp_f32<0x128>(r);
+  return dr::add_rows_f32(r);
 }
 
 // 1 / sqrt(s) for s > 0 (v_rsq_f32, <= 1 ulp; denormal s is scaled into
@@ -212,8 +195,8 @@ __global__ __launch_bounds__(kBlock) void ild_grad_kernel(const GradArgs a) {
           }
         }
         const float c4 = group_sum4(c, gl);
-        const float cq[4] = {dpp_mov<0x00>(c4), dpp_mov<0x55>(c4), dpp_mov<0xAA>(c4),
-                             dpp_mov<0xFF>(c4)};  // quad_perm broadcasts of lanes 0..3
+        const float cq[4] = {dpp_f32<0x00>(c4), dpp_f32<0x55>(c4), dpp_f32<0xAA>(c4),
+                             dpp_f32<0xFF>(c4)};  // quad_perm broadcasts of lanes 0..3
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           if (inv[j] == 0.f) continue;  // no gradient for a zero row (uniform in the group)
@@ -261,8 +244,8 @@ __global__ __launch_bounds__(kBlock) void ild_grad_kernel(const GradArgs a) {
             }
           }
           const float r = rsqrt_or_zero(group_sum4(ss, gl));
-          const float rq[4] = {dpp_mov<0x00>(r), dpp_mov<0x55>(r), dpp_mov<0xAA>(r),
-                               dpp_mov<0xFF>(r)};  // quad_perm broadcasts of lanes 0..3
+          const float rq[4] = {dpp_f32<0x00>(r), dpp_f32<0x55>(r), dpp_f32<0xAA>(r),
+                               dpp_f32<0xFF>(r)};  // quad_perm broadcasts of lanes 0..3
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
 #pragma unroll

@@ -48,15 +48,16 @@ typedef float f32x32 __attribute__((ext_vector_type(32)));
 using dr::bf16x8;
 using dr::f32x16;
 
-// a[lane] max a[lane ^ 32] (v_permlane32_swap: one VALU, no LDS round trip)
+// a[lane] max a[lane ^ 32]
 __device__ __forceinline__ float half_swap_max(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+  const dr::F32Pair r = dr::swap32_f32(x);
+  return fmaxf(r.a, r.b);
 }
 
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
+// not dr::wait_vmcnt<0>(): hipcc merges the builtin's wait into its own and moves an s_barrier
 __device__ __forceinline__ void wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // Diagnostic build (-DDR_MMR_DIAG, a measurement variant library only): per-wave s_memtime cycles

@@ -14,16 +14,6 @@
 
 namespace {
 
-__device__ __forceinline__ bool contains_sorted(const int32_t* __restrict__ list, int n,
-                                                int64_t item) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if ((int64_t)list[mid] < item) lo = mid + 1; else hi = mid;
-  }
-  return lo < n && (int64_t)list[lo] == item;
-}
-
 template <typename R>
 __global__ __launch_bounds__(256) void rank_metrics_kernel(
     const R* __restrict__ recs, int64_t n_users, int k, const int64_t* __restrict__ rowptr,
@@ -39,7 +29,7 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(
   float ap_sum = 0.f, dcg = 0.f, idcg = 0.f;
   for (int b0 = 0; b0 < k; b0 += 64) {
     const int p = b0 + lane;
-    const bool in = p < k && contains_sorted(pos, npos, (int64_t)recs[u * k + p]);
+    const bool in = p < k && dr::sorted_contains(pos, npos, (int64_t)recs[u * k + p]);
     const uint64_t bal = __ballot(in);
     // inclusive prefix count of hits up to position p
     const int pre = carry + (int)__builtin_amdgcn_mbcnt_hi(

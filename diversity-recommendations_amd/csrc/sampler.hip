@@ -36,16 +36,6 @@ __device__ __forceinline__ uint64_t draw_bits(uint64_t seed, int64_t pos, int64_
   return mix64(z + 0x8cb92ba72f3d8dd7ull * (uint64_t)(attempt + 1));
 }
 
-__device__ __forceinline__ bool contains(const int32_t* __restrict__ list, int64_t n,
-                                         int32_t item) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (list[mid] < item) lo = mid + 1; else hi = mid;
-  }
-  return lo < n && list[lo] == item;
-}
-
 // u = users[b]; threads [0, m) of a user draw positives, [m, 2m) negatives.
 __global__ __launch_bounds__(kBlock) void draw_kernel(
     const int64_t* __restrict__ users, int64_t n, const int64_t* __restrict__ pos_rowptr,
@@ -77,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void draw_kernel(
   int32_t pick = -1;
   for (int a = 0; a < kMaxTries; ++a) {
     const int32_t c = (int32_t)(draw_bits(seed, u, j, a) % (uint64_t)n_items);
-    if (!contains(pos_items + p0, np, c) && !(nx && contains(ex, nx, c))) {
+    if (!dr::sorted_contains(pos_items + p0, np, c) && !(nx && dr::sorted_contains(ex, nx, c))) {
       pick = c;
       break;
     }

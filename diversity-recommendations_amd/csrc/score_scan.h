@@ -46,6 +46,9 @@ namespace dr_topk {
 
 using dr::bf16x8;
 using dr::f32x16;
+using dr::sorted_contains;
+using dr::wait_vmcnt;
+using dr::wait_vmcnt_dyn;
 using dr::wave_lds_sync;
 
 // Diagnostic build (-DDR_TOPK_DIAG, libdivrec_hip_diag.so only): per-wave
@@ -237,25 +240,6 @@ __device__ __forceinline__ void lds_waitn(u32x4& v) {
   asm volatile("s_waitcnt lgkmcnt(%c1)" : "+v"(v) : "i"(N) : "memory");
 }
 
-// s_waitcnt vmcnt(N) only (expcnt / lgkmcnt left at their maxima).
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (0x7 << 4) | (0xF << 8));
-}
-// Wait until at most n (wave-uniform) VMEM ops are outstanding, rounding n
-// down to a power of two (waits for a little more than required, always
-// correct): six scalar compares instead of a 64-step ladder at every stage.
-__device__ __forceinline__ void wait_vmcnt_dyn(int n) {
-  if (n >= 32) wait_vmcnt<32>();
-  else if (n >= 16) wait_vmcnt<16>();
-  else if (n >= 8) wait_vmcnt<8>();
-  else if (n >= 4) wait_vmcnt<4>();
-  else if (n >= 2) wait_vmcnt<2>();
-  else if (n >= 1) wait_vmcnt<1>();
-  else wait_vmcnt<0>();
-}
-
 // Wave-uniform 64-bit value, forced into SGPRs.
 __device__ __forceinline__ int64_t uni64(int64_t v) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
@@ -320,16 +304,6 @@ __device__ __forceinline__ void issue_stage(const char* __restrict__ I, int64_t 
     const uint32_t m0 = __builtin_amdgcn_readfirstlane(lds_stage + wave_first * 16);
     dr::lds_dma_b128(base, off, m0);
   }
-}
-
-__device__ __forceinline__ bool sorted_contains(const int32_t* __restrict__ list, int n,
-                                                int32_t item) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (list[mid] < item) lo = mid + 1; else hi = mid;
-  }
-  return lo < n && list[lo] == item;
 }
 
 __device__ __forceinline__ int lane_prefix(uint64_t bal) {  // set bits of bal below this lane

@@ -545,7 +545,7 @@ Plan make_plan(int64_t n_users, int64_t n_items, int w, int k, bool seedable,
   int best_c = 1;
   double best = (double)H / slots + (double)dr::ceil_div(T, slots);
   int max_c = max_c_override > 0 ? max_c_override : kMaxTailChunks;
-  if (const int c = knob_int(DR_KNOB_SCAN_SPLIT, 0); c != 0) max_c = c > 0 ? c : 1;  // A/B knob
+  if (const int c = knob_int(DR_KNOB_SCAN_SPLIT, 0); c > 0) max_c = c;  // A/B knob
   // a head user's finalize already sorts 2048 keys when its flush bound
   // passes 1024 (k >= ~800): the tail may then gather as many
   const int head_flush = std::min(k + kSlack + kFlushGap, p.cap - (int)stage_items);

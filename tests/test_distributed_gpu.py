@@ -25,6 +25,7 @@ import torch
 import torch.multiprocessing as mp
 
 from divrec import ops
+from topk_checks import exact_topk
 
 pytestmark = pytest.mark.gpu
 
@@ -70,19 +71,6 @@ def _rank_main(rank, world, port, nu, ni, d, k, seed, hot_stride, bounds, q):
         raise
 
 
-def _exact(U, I, k):
-    """Exact top-k on the device in float64 (integer tables)."""
-    Ud = torch.from_numpy(U).to("cuda").double()
-    Id = torch.from_numpy(I).to("cuda").double()
-    outi, outs = [], []
-    for b in range(0, Ud.shape[0], 256):
-        S = Ud[b:b + 256] @ Id.T
-        v, o = torch.sort(S, dim=1, descending=True, stable=True)
-        outi.append(o[:, :k].cpu())
-        outs.append(v[:, :k].cpu())
-    return torch.cat(outi).numpy(), torch.cat(outs).numpy()
-
-
 @pytest.mark.parametrize("world,d,hot,uneven", [(2, 128, False, False), (4, 64, True, True),
                                                 (4, 128, True, False), (2, 64, False, True)])
 def test_item_sharded_global_thresholds_on_hip(world, d, hot, uneven):
@@ -118,7 +106,7 @@ def test_item_sharded_global_thresholds_on_hip(world, d, hot, uneven):
     one_s, one_i = ops.score_topk(torch.from_numpy(U).to("cuda").to(torch.bfloat16),
                                   torch.from_numpy(I).to("cuda").to(torch.bfloat16), k)
     one_s, one_i = one_s.cpu().numpy(), one_i.cpu().numpy()
-    ref_i, ref_s = _exact(U, I, k)
+    ref_i, ref_s = exact_topk(U, I, k)
     assert np.array_equal(one_i.astype(np.int64), ref_i)
     seen = np.zeros(nu, dtype=int)
     for rank, ulo, uhi, s, i, _, _ in got:

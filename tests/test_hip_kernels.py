@@ -11,15 +11,11 @@ import torch
 
 import oracle
 from divrec import _backend, ops
-from topk_checks import fp32_row_tol, gap_check
+from topk_checks import assert_same_topk, exact_topk, fp32_row_tol, gap_check, int_table
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-
-
-def _int_table(rng, n, d, lo=-3, hi=3):
-    return rng.integers(lo, hi + 1, size=(n, d)).astype(np.float32)
 
 
 def _bf16(x):
@@ -51,7 +47,7 @@ def test_gather_dot(d, dtype):
 
 def test_gather_dot_integer_exact():
     rng = np.random.default_rng(7)
-    U, I = _int_table(rng, 50, 128), _int_table(rng, 70, 128)
+    U, I = int_table(rng, 50, 128), int_table(rng, 70, 128)
     uid, iid = rng.integers(0, 50, 999), rng.integers(0, 70, 999)
     got = ops.gather_dot(torch.from_numpy(U).to(DEV), torch.from_numpy(I).to(DEV),
                          torch.from_numpy(uid).to(DEV), torch.from_numpy(iid).to(DEV))
@@ -195,7 +191,7 @@ def test_gather_dot_backward_bad_ids_add_nothing(d):
 def test_score_topk_integer_exact(d, k):
     rng = np.random.default_rng(1000 * d + k)
     nu, ni = 37 + d, 2000 + 13  # partial user block, partial item tile
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     s, it = ops.score_topk(_bf16(U), _bf16(I), k)
     ref_i, ref_s = oracle.recommend_topk(U, I, k, return_scores=True)
     assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
@@ -205,7 +201,7 @@ def test_score_topk_integer_exact(d, k):
 def test_score_topk_ties_exact():
     # values in {-1, 0, 1} at d=32: massive ties; order must be score desc, id asc
     rng = np.random.default_rng(11)
-    U, I = _int_table(rng, 70, 32, -1, 1), _int_table(rng, 3000, 32, -1, 1)
+    U, I = int_table(rng, 70, 32, -1, 1), int_table(rng, 3000, 32, -1, 1)
     s, it = ops.score_topk(_bf16(U), _bf16(I), 100)
     ref_i = oracle.recommend_topk(U, I, 100)
     assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
@@ -213,7 +209,7 @@ def test_score_topk_ties_exact():
 
 def test_score_topk_user_ids_and_item_base():
     rng = np.random.default_rng(5)
-    U, I = _int_table(rng, 300, 64), _int_table(rng, 4000, 64)
+    U, I = int_table(rng, 300, 64), int_table(rng, 4000, 64)
     users = np.array([299, 0, 17, 17, 150], dtype=np.int64)
     s, it = ops.score_topk(_bf16(U), _bf16(I), 20, user_ids=torch.from_numpy(users).to(DEV),
                            item_base=1_000_000)
@@ -224,7 +220,7 @@ def test_score_topk_user_ids_and_item_base():
 def test_score_topk_exclusion_exact():
     rng = np.random.default_rng(9)
     nu, ni, d, k = 130, 3000, 64, 50
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     frozen = [rng.choice(ni, size=rng.integers(0, 400), replace=False) for _ in range(nu)]
     # make some excluded items the best ones (worst case for the threshold)
     for u in range(0, nu, 3):
@@ -240,7 +236,7 @@ def test_score_topk_exclusion_exact():
 def test_score_topk_chunked_catalog_exact():
     # large catalog, few users: the planner splits items into chunks and merges
     rng = np.random.default_rng(21)
-    U, I = _int_table(rng, 40, 32), _int_table(rng, 300_001, 32)
+    U, I = int_table(rng, 40, 32), int_table(rng, 300_001, 32)
     s, it = ops.score_topk(_bf16(U), _bf16(I), 100)
     ref_i, ref_s = oracle.recommend_topk(U, I, 100, return_scores=True)
     assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
@@ -258,8 +254,8 @@ def test_score_topk_guess_rescan_exact():
     the lists must equal the oracle's exactly."""
     rng = np.random.default_rng(77)
     d, ni, k = 64, (1 << 18) + 123, 50
-    U = np.concatenate([_int_table(rng, 48, d, 0, 3), _int_table(rng, 48, d, -3, 0)])
-    I = _int_table(rng, ni, d)
+    U = np.concatenate([int_table(rng, 48, d, 0, 3), int_table(rng, 48, d, -3, 0)])
+    I = int_table(rng, ni, d)
     I[np.arange(20) * 32] = 3.0  # hot sample rows
     users = np.concatenate([rng.permutation(96), rng.integers(0, 96, 24)]).astype(np.int64)
     frozen = [rng.choice(ni, size=rng.integers(0, 50), replace=False) for _ in users]
@@ -282,7 +278,7 @@ def test_score_topk_small_catalog_keeps_every_key(nu, ni, d, k, dtype):
     one-row catalog; best items excluded for some users. Exact against the
     oracle (integer tables)."""
     rng = np.random.default_rng(nu + ni + k)
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     t = _f32 if dtype == "f32" else _bf16
     plan = ops.score_topk_plan(nu, ni, torch.float32 if dtype == "f32" else torch.bfloat16, d, k)
     assert plan["cap"] >= ni and plan["head_keys"] >= max(ni, k)
@@ -314,7 +310,7 @@ def test_score_topk_guess_small_k_exact(k, d, dtype, slots):
     rng = np.random.default_rng(k * 100 + d)
     ni = (1 << 18) + 77
     nu = 2 * (2048 if d <= 64 else 1024) + 35 if slots else 150
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     users = np.concatenate([rng.permutation(nu), rng.integers(0, nu, 20)]).astype(np.int64)
     sel = np.arange(0, len(users), max(1, len(users) // 120))  # the users checked
     frozen = [np.zeros(0, np.int64) for _ in users]
@@ -344,27 +340,11 @@ def test_score_topk_many_workgroups_exact(d):
     several user blocks, the last one partial."""
     rng = np.random.default_rng(500 + d)
     nu, ni, k = 4100 + d, 1500 + 7, 10
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     s, it = ops.score_topk(_bf16(U), _bf16(I), k)
     ref_i, ref_s = oracle.recommend_topk(U, I, k, return_scores=True)
     assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
     assert np.array_equal(s.cpu().numpy(), ref_s)
-
-
-def _exact_topk_torch(U, I, k, block=256):
-    """Integer-valued tables: fp32 scores are exact, so a stable descending
-    sort over ascending item ids IS the (score desc, id asc) order. Used where
-    the per-user oracle loop would take minutes; it is pinned to the oracle by
-    test_score_topk_integer_exact's cases."""
-    Ud = torch.from_numpy(U).to(DEV)
-    Id = torch.from_numpy(I).to(DEV)
-    outs, outi = [], []
-    for b in range(0, Ud.shape[0], block):
-        S = Ud[b:b + block] @ Id.T
-        v, i = torch.sort(S, dim=1, descending=True, stable=True)
-        outs.append(v[:, :k].cpu())
-        outi.append(i[:, :k].cpu())
-    return torch.cat(outi).numpy().astype(np.int64), torch.cat(outs).numpy()
 
 
 @pytest.mark.parametrize("d", [32, 64, 128])
@@ -379,22 +359,13 @@ def test_score_topk_nan_rows_never_ranked(d):
     with NaN rows at sample positions too."""
     rng = np.random.default_rng(300 + d)
     nu, ni, k = 3000, 300_011, 50
-    U = _int_table(rng, nu, d)
-    I = _int_table(rng, ni, d)
+    U = int_table(rng, nu, d)
+    I = int_table(rng, ni, d)
     bad = np.unique(np.concatenate([np.arange(0, 40) * 32, rng.choice(ni, 200, replace=False)]))
     I[bad, d // 2] = np.nan
     s, it = ops.score_topk(_bf16(U), _bf16(I), k)
-    it = it.cpu().numpy().astype(np.int64)
-    assert not np.isin(it, bad).any()
-    Ifin = I.copy()
-    Ifin[bad] = 0.0
-    ref_i, ref_s = _exact_topk_torch(U, Ifin, k + len(bad))
-    # the finite items' order: drop the zeroed NaN rows from the exact lists
-    keep = ~np.isin(ref_i, bad)
-    exp_i = np.stack([r[m][:k] for r, m in zip(ref_i, keep)])
-    exp_s = np.stack([r[m][:k] for r, m in zip(ref_s, keep)])
-    assert np.array_equal(it, exp_i)
-    assert np.array_equal(s.cpu().numpy(), exp_s)
+    assert not np.isin(it.cpu().numpy(), bad).any()
+    assert_same_topk(s, it, exact_topk(U, I, k, drop=np.isin(np.arange(ni), bad)))
 
 
 @pytest.mark.parametrize("d", [64, 128])
@@ -405,17 +376,15 @@ def test_score_topk_guess_rescan_many_units_exact(d):
     rng = np.random.default_rng(88 + d)
     ni, k = (1 << 18) + 77, 20
     nu = 2 * (2048 if d <= 64 else 1024) + 333
-    U = _int_table(rng, nu, d, 0, 3)
-    I = _int_table(rng, ni, d)
+    U = int_table(rng, nu, d, 0, 3)
+    I = int_table(rng, ni, d)
     # 12 hot sample rows: the best items of every (non-negative) user. The
     # guess's rank in the sample is ks = ceil(mu + 6 sqrt(mu) + 3) = 9 for
     # k = 20 (mu = k / 32), so the guessed threshold is the hot score and only
     # the 12 hot items (< k) pass it: every user fails and is rescanned.
     I[np.arange(12) * 32] = 3.0
     s, it = ops.score_topk(_bf16(U), _bf16(I), k)
-    ref_i, ref_s = _exact_topk_torch(U, I, k)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
-    assert np.array_equal(s.cpu().numpy(), ref_s)
+    assert_same_topk(s, it, exact_topk(U, I, k))
 
 
 def _Slots(n):
@@ -423,21 +392,6 @@ def _Slots(n):
     dr_set_plan_knob): small counts reach the split-tail plans with small inputs."""
     from divrec import _backend
     return _backend.plan_knobs(scan_slots=n)
-
-
-def _exact_topk_torch_excl(U, I, k, frozen, block=256):
-    """_exact_topk_torch with each user's frozen items scored -inf (integer
-    tables: exact scores, stable sort = (score desc, id asc))."""
-    Ud, Id = torch.from_numpy(U).to(DEV), torch.from_numpy(I).to(DEV)
-    outi = []
-    for b in range(0, Ud.shape[0], block):
-        S = Ud[b:b + block] @ Id.T
-        for r in range(S.shape[0]):
-            f = frozen[b + r]
-            if len(f):
-                S[r, torch.from_numpy(np.asarray(f, dtype=np.int64)).to(DEV)] = -float("inf")
-        outi.append(torch.sort(S, dim=1, descending=True, stable=True).indices[:, :k].cpu())
-    return torch.cat(outi).numpy().astype(np.int64)
 
 
 @pytest.mark.parametrize("d,slots,n_full", [(128, 4, 6), (64, 3, 6), (32, 3, 3), (32, 5, 1)])
@@ -450,7 +404,7 @@ def test_score_topk_split_tail_exact(d, slots, n_full):
     rng = np.random.default_rng(900 + d)
     upwg = 2048 if d <= 64 else 1024
     nu, ni, k = n_full * upwg + 333, 300_007, 50
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     users = np.concatenate([np.arange(nu - 40), rng.integers(0, nu, 40)]).astype(np.int64)
     frozen = [rng.choice(ni, size=int(rng.integers(0, 30)), replace=False) for _ in users]
     for n in range(0, len(users), 97):  # exclude some of the user's best items
@@ -461,8 +415,7 @@ def test_score_topk_split_tail_exact(d, slots, n_full):
         s, it = ops.score_topk(_bf16(U), _bf16(I), k, user_ids=torch.from_numpy(users).to(DEV),
                                exclude=(torch.from_numpy(rowptr).to(DEV),
                                         torch.from_numpy(cols).to(DEV)))
-    ref_i = _exact_topk_torch_excl(U[users], I, k, frozen)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
+    assert_same_topk(s, it, exact_topk(U[users], I, k, frozen=frozen))
 
 
 @pytest.mark.parametrize("d", [64, 128])
@@ -473,26 +426,22 @@ def test_score_topk_split_tail_rescan_exact(d):
     rng = np.random.default_rng(188 + d)
     ni, k = (1 << 18) + 77, 20
     nu = 2 * (2048 if d <= 64 else 1024) + 333
-    U = _int_table(rng, nu, d, 0, 3)
-    I = _int_table(rng, ni, d)
+    U = int_table(rng, nu, d, 0, 3)
+    I = int_table(rng, ni, d)
     I[np.arange(12) * 32] = 3.0  # see test_score_topk_guess_rescan_many_units_exact
     with _Slots(2):
         s, it = ops.score_topk(_bf16(U), _bf16(I), k)
-    ref_i, ref_s = _exact_topk_torch(U, I, k)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
-    assert np.array_equal(s.cpu().numpy(), ref_s)
+    assert_same_topk(s, it, exact_topk(U, I, k))
 
 
 def test_score_topk_split_tail_fp32_exact():
     """The fp32 scan under a split-tail plan."""
     rng = np.random.default_rng(4242)
     nu, ni, k = 2 * 1024 + 100, 300_007, 30
-    U, I = _int_table(rng, nu, 64), _int_table(rng, ni, 64)
+    U, I = int_table(rng, nu, 64), int_table(rng, ni, 64)
     with _Slots(2):
         s, it = ops.score_topk(torch.from_numpy(U).to(DEV), torch.from_numpy(I).to(DEV), k)
-    ref_i, ref_s = _exact_topk_torch(U, I, k)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
-    assert np.array_equal(s.cpu().numpy(), ref_s)
+    assert_same_topk(s, it, exact_topk(U, I, k))
 
 
 def test_score_topk_guess_large_exclusion_exact():
@@ -502,7 +451,7 @@ def test_score_topk_guess_large_exclusion_exact():
     rng = np.random.default_rng(4711)
     d, ni, k = 64, (1 << 19) + 321, 50
     nu = 2 * 2048 + 77
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     users = np.concatenate([np.arange(nu - 30), rng.integers(0, nu, 30)]).astype(np.int64)
     frozen = [rng.choice(ni, size=int(rng.integers(0, 20)), replace=False) for _ in users]
     for n in range(0, len(users), 257):
@@ -511,8 +460,7 @@ def test_score_topk_guess_large_exclusion_exact():
     rowptr, cols = oracle.exclusion_csr(frozen)
     s, it = ops.score_topk(_bf16(U), _bf16(I), k, user_ids=torch.from_numpy(users).to(DEV),
                            exclude=(torch.from_numpy(rowptr).to(DEV), torch.from_numpy(cols).to(DEV)))
-    ref_i = _exact_topk_torch_excl(U[users], I, k, frozen)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
+    assert_same_topk(s, it, exact_topk(U[users], I, k, frozen=frozen))
 
 
 def test_score_topk_guess_hot_sample_rows_exact():
@@ -523,13 +471,11 @@ def test_score_topk_guess_hot_sample_rows_exact():
     rng = np.random.default_rng(99)
     d, ni, k = 64, (1 << 19) + 77, 20
     nu = 2048 + 100
-    U = _int_table(rng, nu, d, 0, 3)
-    I = _int_table(rng, ni, d)
+    U = int_table(rng, nu, d, 0, 3)
+    I = int_table(rng, ni, d)
     I[np.arange(8) * 1024] = 3.0
     s, it = ops.score_topk(_bf16(U), _bf16(I), k)
-    ref_i, ref_s = _exact_topk_torch(U, I, k)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
-    assert np.array_equal(s.cpu().numpy(), ref_s)
+    assert_same_topk(s, it, exact_topk(U, I, k))
 
 
 @pytest.mark.parametrize("d,ni,slots", [(64, 5000, None), (128, 300_007, 2), (32, 300_007, None)])
@@ -540,7 +486,7 @@ def test_score_topk_seeded_thresholds_exact(d, ni, slots):
     too (slots = 2). Integer tables: exact against a masked stable sort."""
     rng = np.random.default_rng(d + ni)
     nu, k = 2 * (2048 if d <= 64 else 1024) + 55, 30
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     Ud, Id = torch.from_numpy(U).to(DEV), torch.from_numpy(I).to(DEV)
     S = Ud @ Id.T
     top = torch.topk(S, 41, dim=1).values
@@ -615,7 +561,7 @@ def test_score_topk_fp32_integer_exact(d, k):
     d=100 runs zero-padded to 128."""
     rng = np.random.default_rng(7000 + 1000 * d + k)
     nu, ni = 37 + d, 2000 + 13
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     s, it = ops.score_topk(_f32(U), _f32(I), k)
     ref_i, ref_s = oracle.recommend_topk(U, I, k, return_scores=True)
     assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
@@ -650,7 +596,7 @@ def test_score_topk_fp32_vs_bf16_mode():
     """bf16-representable fp32 tables: the fp32 scan and the bf16 scan see the
     same values; integer-valued ones give identical lists and scores."""
     rng = np.random.default_rng(44)
-    U, I = _int_table(rng, 300, 128), _int_table(rng, 7000, 128)
+    U, I = int_table(rng, 300, 128), int_table(rng, 7000, 128)
     s32, i32 = ops.score_topk(_f32(U), _f32(I), 50)
     s16, i16 = ops.score_topk(_bf16(U), _bf16(I), 50)
     assert torch.equal(i32, i16) and torch.equal(s32, s16)
@@ -675,7 +621,7 @@ def test_score_topk_k1000_guess_exclusion_exact(d, k, dtype):
     run the staged long-list instance (56-KB stages, round 6)."""
     rng = np.random.default_rng(d + k)
     nu, ni = 24, (1 << 18) + 999
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     frozen = _excl(rng, U, I, nu, ni)
     rowptr, cols = oracle.exclusion_csr(frozen)
     t = _f32 if dtype == "f32" else _bf16
@@ -692,7 +638,7 @@ def test_score_topk_k1000_many_users_exact(dtype):
     guess): fp32 and bf16 scans, exclusion of the best items."""
     rng = np.random.default_rng(1000)
     d, nu, ni, k = 64, 2100, 3000, 1000
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     frozen = _excl(rng, U, I, nu, ni, n_max=100)
     rowptr, cols = oracle.exclusion_csr(frozen)
     t = _f32 if dtype == "f32" else _bf16
@@ -711,7 +657,7 @@ def test_score_topk_sharded_k1000_equals_single_pass():
     merge (8 x 1000 > 2048 entries) — bit-identical to one pass."""
     rng = np.random.default_rng(808)
     d, nu, ni, k = 128, 300, 40000, 1000
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     Ub, Ib = _bf16(U), _bf16(I)
     full_s, full_i = ops.score_topk(Ub, Ib, k)
     bounds = np.linspace(0, ni, 9).astype(int)
@@ -1341,8 +1287,8 @@ def test_sample_thresholds_group_max(d, n_sample, ks1, ks, ids, dense):
 
     rng = np.random.default_rng(d + n_sample + ks)
     nu = 2500
-    U = _int_table(rng, nu, d)
-    Sm = _int_table(rng, n_sample, d)
+    U = int_table(rng, nu, d)
+    Sm = int_table(rng, n_sample, d)
     uids = rng.permutation(nu)[:1800].astype(np.int64) if ids else None
     Ub, Sb = _bf16(U), _bf16(Sm)
     with _backend.plan_knobs(sample_dense=dense):
@@ -1380,7 +1326,7 @@ def test_sample_thresholds_position_ranges_match_dense(n_sample, knobs):
     31 rows hold no whole tile: -inf for every user."""
     rng = np.random.default_rng(n_sample)
     d, ks1, ks, nu = 32, 2, 5, 2 * 2048 + 100
-    Ub, Sb = _bf16(_int_table(rng, nu, d)), _bf16(_int_table(rng, n_sample, d))
+    Ub, Sb = _bf16(int_table(rng, nu, d)), _bf16(int_table(rng, n_sample, d))
     out = {}
     with _backend.plan_knobs(**knobs):
         plan = ops.score_topk_plan(nu, n_sample, torch.bfloat16, d, ks)
@@ -1438,7 +1384,7 @@ def test_score_topk_dense_sample_chunked_units(slots):
     identical lists, and the lists are exact (integer tables)."""
     rng = np.random.default_rng(4242 + slots)
     nu, ni, d, k = 70, 32 * 131072 + 45, 32, 300
-    U, I = _int_table(rng, nu, d), _int_table(rng, ni, d)
+    U, I = int_table(rng, nu, d), int_table(rng, ni, d)
     Ut, It = _bf16(U), _bf16(I)
     # stride 32 forced: k = 300 samples this 4.2M-row catalog at 64 by default
     knobs = {"guess_stride": 32, **({"scan_slots": slots} if slots else {})}
@@ -1452,8 +1398,7 @@ def test_score_topk_dense_sample_chunked_units(slots):
         out.append((s.cpu(), i.cpu()))
     for s, i in out[1:]:
         assert torch.equal(i, out[0][1]) and torch.equal(s, out[0][0])
-    ref_i, ref_s = _exact_topk_torch(U, I, k)
-    assert np.array_equal(out[0][1].numpy().astype(np.int64), ref_i)
+    assert_same_topk(*out[0], exact_topk(U, I, k))
 
 
 @pytest.mark.parametrize("d,k", [(128, 129), (64, 300), (256, 200), (32, 1000), (128, 1000)])

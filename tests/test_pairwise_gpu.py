@@ -319,6 +319,19 @@ def test_rank_metrics_without_any_positive():
         torch.zeros(0, dtype=torch.int32, device=DEV)))
 
 
+@pytest.mark.parametrize("dtype", [torch.int32, torch.int64], ids=["int32", "int64"])
+def test_rank_metrics_positive_rows_of_length_0_1_5(dtype):
+    """3 users x 8 items, k = 4: the listed ids meet their user's sorted
+    positives row at its first entry, at its last entry and nowhere, in an
+    empty row, a row of one and a row of five."""
+    recs = np.array([[0, 1, 2, 3], [3, 0, 5, 7], [1, 7, 5, 0]], dtype=np.int64)
+    rowptr, items = csr([[], [3], [1, 2, 4, 6, 7]])
+    ref = rank_metrics_f64(recs, rowptr, items)
+    assert [round(4 * p) for p in ref[0]] == [0, 1, 2]
+    got = ops.rank_metrics(dev(recs, dtype), dev(rowptr), dev(items))
+    check_rank(host(*got), ref, what=f"short rows {dtype}")
+
+
 # --------------------------------------------------------------------------- catalog histogram
 def _hist_reference(recs, n_items):
     ok = (recs >= 0) & (recs < n_items)
@@ -422,6 +435,24 @@ def test_sample_pairwise_draws_depend_on_seed_and_user_only(exclude):
     tp, tn = sample(twice)
     assert np.array_equal(tp, p[[0, 1, 2, 0, 1, 2, 1]]) and np.array_equal(tn, n[[0, 1, 2, 0, 1, 2, 1]])
     assert len({tuple(r) for r in n.tolist()}) > 30  # users differ from each other
+
+
+def test_sample_pairwise_exclusion_rows_of_length_0_1_5():
+    """3 users x 8 items, m = 4 over 40 seeds (160 draws per user: an allowed
+    item is missed with probability (6/7)^160 < 1e-10): every item is looked
+    up in its user's sorted rows, so the search meets a row's first entry,
+    its last entry and ids around them, in an exclusion row that is empty, of
+    one and of five. Negatives are exactly the allowed items."""
+    pos, frz = [[4], [1], [1]], [[], [6], [0, 2, 3, 5, 7]]
+    pos_csr, excl_csr = [dev(a) for a in csr(pos)], [dev(a) for a in csr(frz)]
+    users = torch.arange(3, device=DEV)
+    seen = [set(), set(), set()]
+    for seed in range(40):
+        p, n, _ = ops.sample_pairwise(users, *pos_csr, 8, 4, seed, exclude=excl_csr, expand=False)
+        assert np.array_equal(p.cpu().numpy(), np.repeat([[4], [1], [1]], 4, axis=1))
+        for u, row in enumerate(n.cpu().numpy()):
+            seen[u] |= set(row.tolist())
+    assert seen == [set(range(8)) - set(pos[u]) - set(frz[u]) for u in range(3)]
 
 
 def test_sample_pairwise_one_or_no_allowed_negative():

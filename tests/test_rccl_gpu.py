@@ -29,6 +29,7 @@ import torch
 import torch.multiprocessing as mp
 
 from divrec import ops
+from topk_checks import assert_same_topk, exact_topk
 
 pytestmark = pytest.mark.gpu
 
@@ -88,17 +89,6 @@ def _child(port, stride, q):
         raise
 
 
-def _exact(U, I, k):
-    Ud = torch.from_numpy(U).to("cuda").double()
-    Id = torch.from_numpy(I).to("cuda").double()
-    outi, outs = [], []
-    for b in range(0, Ud.shape[0], 256):
-        v, o = torch.sort(Ud[b:b + 256] @ Id.T, dim=1, descending=True, stable=True)
-        outi.append(o[:, :k].cpu())
-        outs.append(v[:, :k].cpu())
-    return torch.cat(outi).numpy(), torch.cat(outs).numpy()
-
-
 def test_rccl_exchange_world1_matches_one_device():
     from divrec.distributed import guess_ranks, sample_stride
 
@@ -119,8 +109,7 @@ def test_rccl_exchange_world1_matches_one_device():
     U, I = _tables(stride)
     one_s, one_i = ops.score_topk(torch.from_numpy(U).to("cuda").to(torch.bfloat16),
                                   torch.from_numpy(I).to("cuda").to(torch.bfloat16), K)
-    ref_i, ref_s = _exact(U, I, K)
-    assert np.array_equal(one_i.cpu().numpy().astype(np.int64), ref_i)
+    assert_same_topk(one_s, one_i, exact_topk(U, I, K))
     assert np.array_equal(got["i"], one_i.cpu().numpy())
     assert np.array_equal(got["s"], one_s.cpu().numpy())
     assert got["thr"].shape == (2, NU) and (got["thr"][0] >= got["thr"][1]).all()

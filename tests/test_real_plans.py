@@ -51,7 +51,8 @@ def exact_topk_f64(U64: torch.Tensor, I64: torch.Tensor, k: int, frozen=None, bl
     """Exact (score desc, id asc) top-k of the rows of U64 over I64 (float64
     device tensors holding integers: every score exact). frozen[r]: item ids
     excluded for row r (scored -inf). Returns (items int64 [n, k], scores
-    float64 [n, k]) on the CPU."""
+    float64 [n, k]) on the CPU. Not topk_checks.exact_topk: full-size float64
+    device tables, and top-k-then-filter to bound memory where that one sorts."""
     outi, outs = [], []
     for b in range(0, U64.shape[0], block):
         S = U64[b:b + block] @ I64.T

@@ -13,10 +13,8 @@ counts off the tile, CAP 1024, and one float-table case.
 Every case runs unseeded (ops.score_topk) and through the caller-seeded entry
 (init_thr), at d = 128 bf16. They hold for either MFMA shape.
 
-Integer-valued tables in [-3, 3] make every product and every fp32 partial
-sum exact, so lists and scores must be IDENTICAL (tolerance 0) to the exact
-float64 top-k in (score desc, item id asc) order (the helpers of
-tests/test_scan_survivors.py). The float case uses the gap-aware rule and the
+Integer-valued tables in [-3, 3]: lists and scores must be IDENTICAL (tolerance
+0) to tests/topk_checks.py's exact_topk. The float case uses the gap-aware rule and the
 tolerance of tests/test_hip_kernels.py::test_score_topk_float_tolerance.
 """
 import numpy as np
@@ -24,7 +22,8 @@ import pytest
 import torch
 
 from divrec import ops
-from test_scan_survivors import D, DEV, PLANT, _both, _int_table, _tables
+from test_scan_survivors import D, DEV, PLANT, _both, _tables
+from topk_checks import int_table
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +34,7 @@ def _planted(nu, user, rows, flips):
     far above every other score (|3 * a sum of 128 values in [-3, 3]|, a
     standard deviation of 68)."""
     rng = np.random.default_rng(1600 + 64 * user + rows[0])
-    U, I = _int_table(rng, nu, D), _int_table(rng, 64, D)
+    U, I = int_table(rng, nu, D), int_table(rng, 64, D)
     pat = rng.choice(np.array([-3.0, 3.0], dtype=np.float32), size=D)
     U[user] = pat
     for row, f in zip(rows, flips):
@@ -51,7 +50,7 @@ def test_k_mapping_one_hot_items_exact():
     """Item k is 3 e_k, so user u's score of it is 3 U[u, k]: a k index that
     met another user element, in any k-step or lane group, changes a list."""
     rng = np.random.default_rng(3216)
-    U = _int_table(rng, 64, D)
+    U = int_table(rng, 64, D)
     I = 3.0 * np.eye(D, dtype=np.float32)
     _both(U, I, 32)
 

@@ -11,10 +11,8 @@ short stage, scans from -inf whose every stage floods the buffers (survivor
 stores and compactions between the refills), and seeded scans with a forced
 rescan.
 
-Rule and tolerance are those of tests/test_hip_kernels.py for such shapes:
-integer-valued tables make every bf16 product and every fp32 partial sum exact,
-so scores equal the float64 scores and the lists must be IDENTICAL (tolerance
-0) to the exact float64 top-k in (score desc, item id asc) order.
+Rule and tolerance are those of tests/topk_checks.py: integer-valued tables,
+lists and scores IDENTICAL (tolerance 0) to exact_topk.
 
 Catalogs stay above 2048 rows (at or below, the keep-every-key plan runs and
 nothing is compacted), so the 224-row cases use 10 stages where the 288-row
@@ -27,6 +25,7 @@ import pytest
 import torch
 
 from divrec import _backend, ops
+from topk_checks import assert_same_topk, exact_topk, int_table
 
 pytestmark = pytest.mark.gpu
 
@@ -44,33 +43,14 @@ def _catalogs(k):
 assert _catalogs(100) == [2304, 2305, 2336, 2373, 2591]
 
 
-def _int_table(rng, n, d, lo=-3, hi=3):
-    return rng.integers(lo, hi + 1, size=(n, d)).astype(np.float32)
-
-
 def _bf16(x):
     return torch.from_numpy(x).to(DEV).to(torch.bfloat16)
-
-
-def _exact_topk64(U, I, k, block=128):
-    """Exact float64 top-k on the device, (score desc, item id asc): a stable
-    descending sort over ascending ids. (items int64, scores float64)"""
-    Ud = torch.from_numpy(U).to(DEV).double()
-    Id = torch.from_numpy(I).to(DEV).double()
-    outi, outs = [], []
-    for b in range(0, Ud.shape[0], block):
-        v, i = torch.sort(Ud[b:b + block] @ Id.T, dim=1, descending=True, stable=True)
-        outi.append(i[:, :k].cpu())
-        outs.append(v[:, :k].cpu())
-    return torch.cat(outi).numpy(), torch.cat(outs).numpy()
 
 
 def _check(U, I, k, **knobs):
     with _backend.plan_knobs(**knobs):
         s, it = ops.score_topk(_bf16(U), _bf16(I), k)
-    ref_i, ref_s = _exact_topk64(U, I, k)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
-    assert np.array_equal(s.cpu().numpy().astype(np.float64), ref_s)
+    assert_same_topk(s, it, exact_topk(U, I, k))
 
 
 @functools.lru_cache(maxsize=None)
@@ -81,8 +61,8 @@ def _tables(d, ascending=False):
     floods the buffers (survivor stores after every refill, compactions at
     the stage ends)."""
     rng = np.random.default_rng(1280 + d + (7 if ascending else 0))
-    U = _int_table(rng, NU_MAX, d, 0 if ascending else -3, 3)
-    I = _int_table(rng, 2600, d)
+    U = int_table(rng, NU_MAX, d, 0 if ascending else -3, 3)
+    I = int_table(rng, 2600, d)
     if ascending:
         I = I[np.argsort(I.sum(axis=1), kind="stable")]
     return U, I
@@ -93,7 +73,7 @@ def _small_ref(d, k, ni, ascending=False):
     """Exact lists of all NU_MAX users over the first ni rows (shared by the
     user counts: a user's list does not depend on the other users)."""
     U, I = _tables(d, ascending)
-    return _exact_topk64(U, I[:ni], k)
+    return exact_topk(U, I[:ni], k)
 
 
 @pytest.mark.parametrize("nu", [1, 33, 1024, 1100])
@@ -109,8 +89,7 @@ def test_stage_counts_exact(k, stage_case, nu):
     U, I = _tables(128)
     s, it = ops.score_topk(_bf16(U[:nu]), _bf16(I[:ni]), k)
     ref_i, ref_s = _small_ref(128, k, ni)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i[:nu])
-    assert np.array_equal(s.cpu().numpy().astype(np.float64), ref_s[:nu])
+    assert_same_topk(s, it, (ref_i[:nu], ref_s[:nu]))
 
 
 @pytest.mark.parametrize("k", [100, 1000])
@@ -140,8 +119,7 @@ def test_flooding_stages_exact(k):
     assert sure.min() >= 1 and np.median(sure) >= (3 if k == 100 else 1)
     s, it = ops.score_topk(_bf16(U), _bf16(I[:ni]), k)
     ref_i, ref_s = _small_ref(128, k, ni, True)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
-    assert np.array_equal(s.cpu().numpy().astype(np.float64), ref_s)
+    assert_same_topk(s, it, (ref_i, ref_s))
 
 
 @pytest.mark.parametrize("k,ni", [(100, 29 * 288 + 28 * 288 + 37), (1000, 37 * 224 + 36 * 224 + 37)])
@@ -150,7 +128,7 @@ def test_split_tail_short_last_stage_exact(k, ni):
     two chunk units. The second starts mid-catalog (row 8352 / 8288) and ends
     with a stage of one tile + 5 rows."""
     rng = np.random.default_rng(4100 + k)
-    U, I = _int_table(rng, NU_MAX, 128), _int_table(rng, ni, 128)
+    U, I = int_table(rng, NU_MAX, 128), int_table(rng, ni, 128)
     with _backend.plan_knobs(scan_slots=4):
         plan = ops.score_topk_plan(NU_MAX, ni, torch.bfloat16, 128, k)
     assert plan["tail_chunks"] == 2 and plan["head_blocks"] == 0
@@ -165,7 +143,7 @@ def test_seeded_scan_exact(k, ni):
     rng = np.random.default_rng(4200 + k)
     plan = ops.score_topk_plan(NU_MAX, ni, torch.bfloat16, 128, k)
     assert plan["sample_stride"] > 0
-    _check(_int_table(rng, NU_MAX, 128), _int_table(rng, ni, 128), k)
+    _check(int_table(rng, NU_MAX, 128), int_table(rng, ni, 128), k)
 
 
 @pytest.mark.parametrize("slots", [None, 3])
@@ -179,8 +157,8 @@ def test_forced_rescan_from_minus_inf_exact(slots):
     user."""
     rng = np.random.default_rng(4300)
     ni, k = 911 * 288 + 37, 100
-    U = _int_table(rng, NU_MAX, 128, 0, 3)
-    I = _int_table(rng, ni, 128)
+    U = int_table(rng, NU_MAX, 128, 0, 3)
+    I = int_table(rng, ni, 128)
     plan = ops.score_topk_plan(NU_MAX, ni, torch.bfloat16, 128, k)
     assert plan["sample_stride"] == 32 and plan["sample_rank"] < 30
     I[np.arange(30) * 32] = 3.0  # 30 hot sample rows >= the sample rank, < k
@@ -189,9 +167,7 @@ def test_forced_rescan_from_minus_inf_exact(slots):
         s, it = ops.score_topk(_bf16(U), _bf16(I), k, stats=stats)
     print("guess failures", stats["guess_failures"])
     assert stats["guess_failures"] == [NU_MAX, NU_MAX]  # both tiers failed: rescanned from -inf
-    ref_i, ref_s = _exact_topk64(U, I, k)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
-    assert np.array_equal(s.cpu().numpy().astype(np.float64), ref_s)
+    assert_same_topk(s, it, exact_topk(U, I, k))
 
 
 @pytest.mark.parametrize("d", [64, 256])
@@ -204,5 +180,4 @@ def test_other_widths_keep_their_boundary_exact(d):
     U, I = _tables(d)
     s, it = ops.score_topk(_bf16(U), _bf16(I[:ni]), 100)
     ref_i, ref_s = _small_ref(d, 100, ni)
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
-    assert np.array_equal(s.cpu().numpy().astype(np.float64), ref_s)
+    assert_same_topk(s, it, (ref_i, ref_s))

@@ -14,10 +14,8 @@ counters of the waves that issue nothing and the ring restart carry over),
 split tails, a seeded scan whose every user is rescanned, and one d = 64 and
 one fp32 d = 128 case for the instances that keep eight issuers.
 
-Rule and tolerance are those of tests/test_scan_refill.py: integer-valued
-tables make every product and every fp32 partial sum exact, so lists and scores
-must be IDENTICAL (tolerance 0) to the exact float64 top-k in (score desc,
-item id asc) order; where k exceeds the catalog the tail is item -1, -inf.
+Rule and tolerance are those of tests/topk_checks.py: integer-valued tables,
+lists and scores IDENTICAL (tolerance 0) to exact_topk.
 """
 import functools
 
@@ -26,16 +24,13 @@ import pytest
 import torch
 
 from divrec import _backend, ops
+from topk_checks import assert_same_topk, exact_topk, int_table
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 NU_MAX = 2100  # three workgroups' users at d = 128 (1024 per workgroup)
 STAGE = 288    # rows per stage of the CAP-512 d = 128 instance
-
-
-def _int_table(rng, n, d, lo=-3, hi=3):
-    return rng.integers(lo, hi + 1, size=(n, d)).astype(np.float32)
 
 
 def _bf16(x):
@@ -46,31 +41,10 @@ def _f32(x):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(DEV)
 
 
-def _exact_topk64(U, I, k, block=128):
-    """Exact float64 top-k on the device, (score desc, item id asc): a stable
-    descending sort over ascending ids; k above the catalog pads with item -1,
-    score -inf. (items int64, scores float64)"""
-    Ud = torch.from_numpy(U).to(DEV).double()
-    Id = torch.from_numpy(I).to(DEV).double()
-    m = min(k, I.shape[0])
-    outi = np.full((U.shape[0], k), -1, dtype=np.int64)
-    outs = np.full((U.shape[0], k), -np.inf, dtype=np.float64)
-    for b in range(0, Ud.shape[0], block):
-        v, i = torch.sort(Ud[b:b + block] @ Id.T, dim=1, descending=True, stable=True)
-        outi[b:b + block, :m] = i[:, :m].cpu().numpy()
-        outs[b:b + block, :m] = v[:, :m].cpu().numpy()
-    return outi, outs
-
-
-def _same(s, it, ref_i, ref_s):
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref_i)
-    assert np.array_equal(s.cpu().numpy().astype(np.float64), ref_s)
-
-
 @functools.lru_cache(maxsize=None)
 def _tables(d):
     rng = np.random.default_rng(1290 + d)
-    return _int_table(rng, NU_MAX, d), _int_table(rng, 2400, d)
+    return int_table(rng, NU_MAX, d), int_table(rng, 2400, d)
 
 
 @functools.lru_cache(maxsize=None)
@@ -78,7 +52,7 @@ def _small_ref(d, k, ni):
     """Exact lists of all NU_MAX users over the first ni rows (shared by the
     user counts: a user's list does not depend on the other users)."""
     U, I = _tables(d)
-    return _exact_topk64(U, I[:ni], k)
+    return exact_topk(U, I[:ni], k)
 
 
 @pytest.mark.parametrize("extra", [15, 16, 17, 31])
@@ -92,7 +66,7 @@ def test_slice_end_inside_a_tile_half_exact(extra):
     U, I = _tables(128)
     s, it = ops.score_topk(_bf16(U[:nu]), _bf16(I[:ni]), k)
     ref_i, ref_s = _small_ref(128, k, ni)
-    _same(s, it, ref_i[:nu], ref_s[:nu])
+    assert_same_topk(s, it, (ref_i[:nu], ref_s[:nu]))
 
 
 @pytest.mark.parametrize("nu", [33, 1100])
@@ -110,7 +84,7 @@ def test_one_stage_and_shorter_exact(ni, nu):
                    torch.zeros(0, dtype=torch.int32, device=DEV))
     s, it = ops.score_topk(_bf16(U[:nu]), _bf16(I[:ni]), k, exclude=exclude)
     ref_i, ref_s = _small_ref(128, k, ni)
-    _same(s, it, ref_i[:nu], ref_s[:nu])
+    assert_same_topk(s, it, (ref_i[:nu], ref_s[:nu]))
 
 
 @pytest.mark.parametrize("slots", [1, 2])
@@ -125,7 +99,7 @@ def test_consecutive_units_on_one_workgroup_exact(slots):
         assert plan["cap"] == 512
         s, it = ops.score_topk(_bf16(U), _bf16(I[:ni]), k)
     ref_i, ref_s = _small_ref(128, k, ni)
-    _same(s, it, ref_i, ref_s)
+    assert_same_topk(s, it, (ref_i, ref_s))
 
 
 @pytest.mark.parametrize("extra", [15, 17])
@@ -135,13 +109,13 @@ def test_split_tail_exact(extra):
     15 / 17 rows."""
     ni, k, nu = 29 * STAGE + 28 * STAGE + extra, 100, 1100
     rng = np.random.default_rng(4400 + extra)
-    U, I = _int_table(rng, nu, 128), _int_table(rng, ni, 128)
+    U, I = int_table(rng, nu, 128), int_table(rng, ni, 128)
     with _backend.plan_knobs(scan_slots=4):
         plan = ops.score_topk_plan(nu, ni, torch.bfloat16, 128, k)
         assert plan["tail_chunks"] == 2 and plan["head_blocks"] == 0
         assert plan["chunk_items"] % STAGE == 0 and (ni - plan["chunk_items"]) % STAGE == extra
         s, it = ops.score_topk(_bf16(U), _bf16(I), k)
-    _same(s, it, *_exact_topk64(U, I, k))
+    assert_same_topk(s, it, exact_topk(U, I, k))
 
 
 @pytest.mark.parametrize("extra,slots", [(15, None), (17, 3)])
@@ -152,8 +126,8 @@ def test_seeded_scan_forced_rescan_exact(extra, slots):
     device-planned chunks. The catalog ends 15 / 17 rows into a stage."""
     rng = np.random.default_rng(4500 + extra)
     ni, k, nu = 911 * STAGE + extra, 100, 1100
-    U = _int_table(rng, nu, 128, 0, 3)
-    I = _int_table(rng, ni, 128)
+    U = int_table(rng, nu, 128, 0, 3)
+    I = int_table(rng, ni, 128)
     plan = ops.score_topk_plan(nu, ni, torch.bfloat16, 128, k)
     assert plan["sample_stride"] == 32 and plan["sample_rank"] < 30
     I[np.arange(30) * 32] = 3.0  # 30 hot sample rows >= the sample rank, < k
@@ -161,7 +135,7 @@ def test_seeded_scan_forced_rescan_exact(extra, slots):
     with _backend.plan_knobs(**({"scan_slots": slots} if slots else {})):
         s, it = ops.score_topk(_bf16(U), _bf16(I), k, stats=stats)
     assert stats["guess_failures"] == [nu, nu]  # both tiers failed: rescanned from -inf
-    _same(s, it, *_exact_topk64(U, I, k))
+    assert_same_topk(s, it, exact_topk(U, I, k))
 
 
 @pytest.mark.parametrize("d,dtype,ni", [(64, "bf16", 5 * 448 + 15), (128, "f32", 33 * 64 + 17)])
@@ -174,4 +148,4 @@ def test_eight_issuer_instances_exact(d, dtype, ni):
     t = _f32 if dtype == "f32" else _bf16
     s, it = ops.score_topk(t(U[:nu]), t(I[:ni]), k)
     ref_i, ref_s = _small_ref(d, k, ni)
-    _same(s, it, ref_i[:nu], ref_s[:nu])
+    assert_same_topk(s, it, (ref_i[:nu], ref_s[:nu]))

@@ -15,10 +15,8 @@ d = 64, the staged path).
 Every shape runs unseeded (ops.score_topk) and through the caller-seeded
 entry (init_thr): both kernel instantiations.
 
-Rule and tolerance are those of tests/test_scan_refill_half.py: integer-valued
-tables make every product and every fp32 partial sum exact, so lists and scores
-must be IDENTICAL (tolerance 0) to the exact float64 top-k in (score desc,
-item id asc) order; slots past the last ranked item are item -1, score -inf.
+Rule and tolerance are those of tests/topk_checks.py: integer-valued tables,
+lists and scores IDENTICAL (tolerance 0) to exact_topk.
 """
 import functools
 
@@ -27,6 +25,7 @@ import pytest
 import torch
 
 from divrec import ops
+from topk_checks import assert_same_topk, exact_topk, int_table
 
 pytestmark = pytest.mark.gpu
 
@@ -35,45 +34,8 @@ D = 128
 PLANT = 9 * D  # score of a planted (user, item) pair: every product is 3 * 3
 
 
-def _int_table(rng, n, d):
-    return rng.integers(-3, 4, size=(n, d)).astype(np.float32)
-
-
 def _dev(x, dtype=torch.bfloat16):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(DEV).to(dtype)
-
-
-def _exact(U, I, k, thr=None, drop=None, block=256):
-    """Exact float64 top-k on the device, (score desc, item id asc): a stable
-    descending sort over ascending ids. drop: bool [users, items] (or
-    [items]) of pairs never ranked; thr: float [users], only scores strictly
-    above it are ranked. Unranked slots are item -1, score -inf.
-    (items int64, scores float64)"""
-    Ud = torch.from_numpy(np.asarray(U, dtype=np.float64)).to(DEV)
-    Id = torch.from_numpy(np.nan_to_num(np.asarray(I, dtype=np.float64))).to(DEV)
-    nu, ni = U.shape[0], I.shape[0]
-    m = min(k, ni)
-    outi = np.full((nu, k), -1, dtype=np.int64)
-    outs = np.full((nu, k), -np.inf, dtype=np.float64)
-    dropd = None if drop is None else torch.from_numpy(np.asarray(drop)).to(DEV)
-    thrd = None if thr is None else torch.from_numpy(np.asarray(thr, dtype=np.float64)).to(DEV)
-    for b in range(0, nu, block):
-        sc = Ud[b:b + block] @ Id.T
-        if dropd is not None:
-            sc = sc.masked_fill(dropd if dropd.dim() == 1 else dropd[b:b + block], -np.inf)
-        if thrd is not None:
-            sc = sc.masked_fill(~(sc > thrd[b:b + block, None]), -np.inf)
-        v, i = torch.sort(sc, dim=1, descending=True, stable=True)
-        v, i = v[:, :m], i[:, :m]
-        i = torch.where(torch.isinf(v), torch.full_like(i, -1), i)
-        outi[b:b + block, :m] = i.cpu().numpy()
-        outs[b:b + block, :m] = v.cpu().numpy()
-    return outi, outs
-
-
-def _same(s, it, ref):
-    assert np.array_equal(it.cpu().numpy().astype(np.int64), ref[0])
-    assert np.array_equal(s.cpu().numpy().astype(np.float64), ref[1])
 
 
 def _empty_csr(nu):
@@ -88,16 +50,16 @@ def _both(U, I, k, thr=None, drop=None, exclude=None, dtype=torch.bfloat16):
     Ut, It = _dev(U, dtype), _dev(I, dtype)
     ex = exclude if exclude is not None or k <= ni else _empty_csr(nu)
     s, it = ops.score_topk(Ut, It, k, exclude=ex)
-    _same(s, it, _exact(U, I, k, drop=drop))
+    assert_same_topk(s, it, exact_topk(U, I, k, drop=drop))
     t = np.full(nu, -np.inf, dtype=np.float32) if thr is None else np.asarray(thr, np.float32)
     s, it = ops.score_topk(Ut, It, k, exclude=exclude, init_thr=torch.from_numpy(t).to(DEV))
-    _same(s, it, _exact(U, I, k, thr=t, drop=drop))
+    assert_same_topk(s, it, exact_topk(U, I, k, thr=t, drop=drop))
 
 
 @functools.lru_cache(maxsize=None)
 def _tables(d=D):
     rng = np.random.default_rng(5150 + d)
-    return _int_table(rng, 2100, d), _int_table(rng, 2405, d)
+    return int_table(rng, 2100, d), int_table(rng, 2405, d)
 
 
 def _planted(user, rows, flips):
@@ -106,7 +68,7 @@ def _planted(user, rows, flips):
     far above every other score (|3 * a sum of 128 values in [-3, 3]|, a
     standard deviation of 68)."""
     rng = np.random.default_rng(77 + 64 * user + rows[0])
-    U, I = _int_table(rng, 32, D), _int_table(rng, 64, D)
+    U, I = int_table(rng, 32, D), int_table(rng, 64, D)
     pat = rng.choice(np.array([-3.0, 3.0], dtype=np.float32), size=D)
     U[user] = pat
     for row, f in zip(rows, flips):
@@ -184,12 +146,74 @@ def test_counters_across_stages_compactions_and_units_exact(excl):
     _both(U, I, k, drop=drop, exclude=exclude)
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+def test_exclusion_rows_of_length_0_1_5_exact(dtype):
+    """3 users x 8 items, k = 4, exclusion rows that are empty, of one and of
+    five (three items left: a padded list). A catalog this small is never
+    compacted, so the rows are searched by the finalize's drop_excluded alone,
+    not by dr::sorted_contains: the next test reaches that one."""
+    rng = np.random.default_rng(808)
+    U, I = int_table(rng, 3, D), int_table(rng, 8, D)
+    rows = [[], [3], [1, 2, 4, 6, 7]]
+    drop = np.zeros((3, 8), dtype=bool)
+    for u, r in enumerate(rows):
+        drop[u, r] = True
+    exclude = (torch.tensor([0, 0, 1, 6], dtype=torch.int64, device=DEV),
+               torch.tensor(sum(rows, []), dtype=torch.int32, device=DEV))
+    _both(U, I, 4, drop=drop, exclude=exclude, dtype=dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+def test_exclusion_rows_of_length_0_1_5_in_a_compaction_exact(dtype):
+    """The compaction's search of the exclusion rows (dr::sorted_contains): 3
+    users x 2100 items, k = 4, rows that are empty, of one and of five.
+
+    That a compaction runs with the planted rows in the buffer follows from the
+    plan: above 2048 items no plan keeps every key; a threshold stays -inf
+    until its buffer's first compaction, which comes at the end of the first
+    stage that leaves more than k + 32 + 96 = 132 keys, so until then every row
+    is stored, rows 0..63 (the shortest stage) among them. That compaction
+    looks every stored id up in the user's row: its first entry, its last
+    entry, the ids between, below and above them.
+
+    What a wrong answer does: the planted rows score 1024 and more, every other
+    row below 512. User 2's row excludes its five planted rows; user 1's
+    excludes the best of its four. An entry the search misses leaves k planted
+    keys in the buffer, the new threshold rises above every other score, and
+    the list ends short (the finalize drops the excluded keys by a search of
+    its own). An id found that is not in the row loses a stored key."""
+    ni, k = 2100, 4
+    rng = np.random.default_rng(909)
+    U, I = int_table(rng, 3, D), int_table(rng, ni, D)
+    rows = [[], [30], [1, 9, 22, 40, 63]]
+    planted = {1: ([30, 3, 31, 50], [0, 1, 2, 3]), 2: (rows[2], [0, 0, 1, 1, 2])}
+    for u, (rws, flips) in planted.items():
+        U[u] = rng.choice(np.array([-3.0, 3.0], dtype=np.float32), size=D)
+        for row, f in zip(rws, flips):
+            I[row] = U[u]
+            I[row, :f] = -U[u, :f]
+    sc = U.astype(np.float64) @ I.astype(np.float64).T
+    for u, (rws, flips) in planted.items():
+        assert np.array_equal(sc[u, rws], PLANT - 18.0 * np.asarray(flips))
+        assert sc[u, rws].min() >= 1024
+        sc[u, rws] = -np.inf
+    assert sc.max() < 512
+    plan = ops.score_topk_plan(3, ni, dtype, D, k)
+    assert plan["tail_chunks"] == 1 and plan["sample_stride"] == 0 and plan["head_keys"] < ni
+    drop = np.zeros((3, ni), dtype=bool)
+    for u, r in enumerate(rows):
+        drop[u, r] = True
+    exclude = (torch.tensor([0, 0, 1, 6], dtype=torch.int64, device=DEV),
+               torch.tensor(sum(rows, []), dtype=torch.int32, device=DEV))
+    _both(U, I, k, drop=drop, exclude=exclude, dtype=dtype)
+
+
 def test_split_units_exact():
     """One user block on a many-CU grid: the catalog is split into chunk
     units, each compacted to end_keep keys at its end."""
     nu, ni, k = 200, 16384 + 37, 100
     rng = np.random.default_rng(616)
-    U, I = _int_table(rng, nu, D), _int_table(rng, ni, D)
+    U, I = int_table(rng, nu, D), int_table(rng, ni, D)
     assert ops.score_topk_plan(nu, ni, torch.bfloat16, D, k)["tail_chunks"] > 1
     _both(U, I, k)
 
