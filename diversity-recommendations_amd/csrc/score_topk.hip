@@ -21,7 +21,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "score_scan.h"
+#include "score_scan_plan.h"
 
 namespace {
 
@@ -452,15 +452,11 @@ int scan_slots() {  // an override, not the cap of dr::persistent_cus() (common.
   return slots > 0 ? slots : dr::device_cus();
 }
 
-int64_t stage_items_for(int w, int cap) {
-  return (int64_t)(stage_bytes_for(w, cap) / (kTileItems * w * 2)) * kTileItems;
-}
-
 // Smallest candidate capacity that leaves at least 32 keys of headroom above
 // k + kSlack once a stage's worth of new keys (the margin) is reserved.
 int cap_for(int w, int k) {
   for (int cap = 512; cap <= 2048; cap <<= 1)
-    if (k + kSlack + 32 <= cap - (int)stage_items_for(w, cap)) return cap;
+    if (k + kSlack + 32 <= cap - stage_items(w, cap)) return cap;
   return -1;
 }
 
@@ -520,11 +516,11 @@ Plan make_plan(int64_t n_users, int64_t n_items, int w, int k, bool seedable,
     p.all_keys = n_items;
     while (p.cap < n_items) p.cap <<= 1;
   }
-  p.users_per_wg = nut_for(w) * 32 * kWavesScan;
+  p.users_per_wg = users_per_wg(w);
   p.n_ublocks = dr::ceil_div(n_users, p.users_per_wg);
   p.n_users_pad = p.n_ublocks * p.users_per_wg;
   const int64_t slots = scan_slots();
-  const int64_t stage_items = stage_items_for(w, p.cap);
+  const int64_t stage_items = dr_topk::stage_items(w, p.cap);
   int max_c_override = 0;
   const int64_t B = p.n_ublocks;
   const int64_t H = (B / slots) * slots;
@@ -597,7 +593,7 @@ int flush_keys(const Plan& p, int w, int k) {
   // never compacted: every row's key (and rank k reached: every output slot written)
   if (p.keep_all) return (int)std::max<int64_t>(p.all_keys, k);
   const int f = k + p.slack + p.gap;
-  const int m = p.cap - (int)stage_items_for(w, p.cap);
+  const int m = p.cap - stage_items(w, p.cap);
   return f < m ? f : m;
 }
 int head_keys(const Plan& p, int w, int k) {
@@ -1247,7 +1243,7 @@ extern "C" int dr_score_topk(const void* user_table, const int64_t* user_ids, in
     p2.grid = scan_slots();
     DR_TRY(run_scan(fn, p2, a2, dtype, w, true, s));
     const DevSplitArgs dsa{p.users_per_wg, p2.grid, kMaxRescanChunks,
-                           a2.buf_blocks,  n_items, stage_items_for(w, p.cap)};
+                           a2.buf_blocks,  n_items, stage_items(w, p.cap)};
     hipLaunchKernelGGL(topk_finalize_stream_kernel, dim3((unsigned)dr::ceil_div(n_users, 4)),
                        dim3(256), 0, s, a.cand, a.cnt, dsa, p.cap, n_users, k, excl_rowptr,
                        excl_items, out_scores, out_items, fail1.pos, fail1.cnt, fail1.rows,

@@ -4,7 +4,7 @@ hazards of tests/fixtures/asm_hazard_fixture.hip (an in-flight inline-asm
 ds_read destination copied before its retiring s_waitcnt; inline asm reading
 an MFMA result without wait states), pass their correct twins, and find no
 hazard and no hot-loop spill in any product score_scan_kernel /
-mmr_pick_kernel instantiation (csrc/score_scan.h:188-202 ds_read_b128_asm +
+mmr_pick_kernel instantiation (csrc/score_scan.h ds_read_b128_asm +
 lds_wait, csrc/mmr.hip's asm round loop)."""
 import os
 import sys

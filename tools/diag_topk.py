@@ -26,7 +26,7 @@ from divrec import _backend as B  # noqa: E402
 SLOTS = ["total", "prologue", "boundary", "mma_issue", "hits", "enqueue", "drain", "flush",
          "n_tiles", "n_enqueue", "n_drain", "n_flush", "n_stages", "realtime_100mhz",
          "b_vmcnt_wait", "b_barrier_wait", "b_dma_issue", "b_exit_to_first_mfma"]
-NSLOT = 24  # kDgSlots (csrc/score_scan.h)
+NSLOT = 24  # kDgSlots (csrc/score_scan_plan.h)
 BOUNDARY = SLOTS[14:18]  # the stage boundary's four parts
 
 
