@@ -76,6 +76,22 @@ __device__ __forceinline__ bool sorted_contains(const int32_t* __restrict__ list
   return lo < n && (T)list[lo] == item;
 }
 
+// Counter-based draws (sampler.hip, warp.hip): 64 bits from a hash of (seed,
+// position, draw, attempt), the same on the host and on the device, so a draw
+// depends on no launch geometry.
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+
+__host__ __device__ __forceinline__ uint64_t draw_bits(uint64_t seed, int64_t pos, int64_t draw,
+                                                       int64_t attempt) {
+  uint64_t z = mix64(seed + 0x9e3779b97f4a7c15ull * (uint64_t)(pos + 1));
+  z = mix64(z ^ (0xd1b54a32d192ed03ull * (uint64_t)(draw + 1)));
+  return mix64(z + 0x8cb92ba72f3d8dd7ull * (uint64_t)(attempt + 1));
+}
+
 // LDS written by the lanes of a wave is visible to its other lanes after this
 // (one wave's private LDS area: no workgroup barrier).
 __device__ __forceinline__ void wave_lds_sync() {

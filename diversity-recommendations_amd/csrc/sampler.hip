@@ -23,18 +23,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxTries = 4096;  // rejection tries per negative draw
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint64_t draw_bits(uint64_t seed, int64_t pos, int64_t draw,
-                                              int64_t attempt) {
-  uint64_t z = mix64(seed + 0x9e3779b97f4a7c15ull * (uint64_t)(pos + 1));
-  z = mix64(z ^ (0xd1b54a32d192ed03ull * (uint64_t)(draw + 1)));
-  return mix64(z + 0x8cb92ba72f3d8dd7ull * (uint64_t)(attempt + 1));
-}
+using dr::draw_bits;  // the counter-based hash (common.h)
 
 // u = users[b]; threads [0, m) of a user draw positives, [m, 2m) negatives.
 __global__ __launch_bounds__(kBlock) void draw_kernel(

@@ -73,6 +73,10 @@ SIGNATURES = {
                               _p, _p]),
     "dr_mse_fwd_bwd": (_i32, [_p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _f32, _p, _p, _p, _p,
                               _p, _p]),
+    "dr_warp_fwd_bwd": (_i32, [_p, _i64, _p, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p, _i32, _f32,
+                               ctypes.c_uint64, _i64, _f32, _p, _p, _p, _p, _p, _p, _p]),
+    "dr_warp_candidates": (_i32, [ctypes.c_uint64, _i64, _i64, _i32, _i64, _p]),
+    "dr_warp_round": (_i32, []),
     "dr_adam_dense": (_i32, [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _p]),
     "dr_sample_pairwise": (_i32, [_p, _i64, _p, _p, _p, _p, _i64, _i32, ctypes.c_uint64, _p, _p,
                                   _p, _p, _p, _p, _p]),

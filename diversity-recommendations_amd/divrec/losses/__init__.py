@@ -13,8 +13,10 @@ from .intra_list_diversity_score import (
 )
 from .log_sigmoid_difference_loss import LogSigmoidDifferenceLoss
 from .mse_loss import MSELoss
+from .warp_loss import WARPLoss
 
 __all__ = [
+    "WARPLoss",
     "LogSigmoidDifferenceLoss",
     "IntraListDiversityScore",
     "IntraListBinaryUnfairnessScore",

@@ -545,6 +545,87 @@ def bpr_fwd_bwd(
     return loss, hit
 
 
+# --------------------------------------------------------------------------- WARP
+WARP_MAX_TRIALS = 4096  # dr_warp_fwd_bwd's largest max_trials (include/divrec_hip.h)
+
+
+def _user_csr(csr, n_users: int, name: str):
+    """An optional per-user CSR (rowptr int64 [n_users + 1], items int32): the
+    two tensors, contiguous, or (None, None)."""
+    if csr is None:
+        return None, None
+    rowptr, items = csr
+    _need(rowptr.dtype == torch.int64 and items.dtype == torch.int32,
+          f"{name} CSR must be int64 rowptr / int32 items")
+    _need(rowptr.dim() == 1 and rowptr.numel() == n_users + 1 and items.dim() == 1,
+          f"{name} CSR must have one row per user row of the table")
+    return rowptr.contiguous(), items.contiguous()
+
+
+def warp_fwd_bwd(
+    user_table: torch.Tensor,
+    item_table: torch.Tensor,
+    user_id: torch.Tensor,
+    pos_id: torch.Tensor,
+    positives: Optional[Tuple[torch.Tensor, torch.Tensor]],
+    exclude: Optional[Tuple[torch.Tensor, torch.Tensor]],
+    max_trials: int,
+    margin: float,
+    seed: int,
+    pair_base: int,
+    grad_scale: float,
+    grad_user: Optional[torch.Tensor],
+    grad_item: Optional[torch.Tensor],
+    err: Optional[torch.Tensor] = None,
+    check: bool = True,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Fused WARP forward + backward (dr_warp_fwd_bwd, whose header comment is
+    the specification); returns per-pair (loss fp32, neg_id int64, trials
+    int32) and accumulates the violating triples' dense gradients into
+    grad_user / grad_item (either may be None). ``positives`` / ``exclude``:
+    per-user CSRs (rowptr int64 [n_users + 1], items int32 sorted per row) of
+    items a draw skips, or None. A pair without a violator within
+    ``max_trials`` draws has loss 0, neg_id -1 and adds nothing. Ids are
+    range-checked on the device (an invalid pair adds nothing): with ``check``
+    and no ``err`` the call reads the count (one sync) and raises IndexError;
+    otherwise the count goes to the caller's ``err`` (may be None), checked by
+    the caller (warp_train_loop: once per epoch)."""
+    dev = B.require_device(user_table, item_table, user_id, pos_id, grad_user, grad_item,
+                           *(positives or ()), *(exclude or ()))
+    _table_pair(user_table, item_table, (torch.float32,), "fp32 tables")
+    user_id, pos_id = _id_columns((user_id, pos_id))
+    n = user_id.numel()
+    _grad_like(grad_user, user_table, "grad_user"), _grad_like(grad_item, item_table, "grad_item")
+    _need(1 <= int(max_trials) <= WARP_MAX_TRIALS, f"max_trials must be in [1, {WARP_MAX_TRIALS}]")
+    _need(int(pair_base) >= 0, "pair_base must be >= 0")
+    pr, pi = _user_csr(positives, user_table.size(0), "positives")
+    er, ei = _user_csr(exclude, user_table.size(0), "exclude")
+    loss = torch.empty(n, dtype=torch.float32, device=dev)
+    neg = torch.empty(n, dtype=torch.int64, device=dev)
+    trials = torch.empty(n, dtype=torch.int32, device=dev)
+    err, own = _counter(dev, err, check)
+    rc = B.lib().dr_warp_fwd_bwd(
+        user_table.data_ptr(), user_table.size(0), item_table.data_ptr(), item_table.size(0),
+        user_table.size(1), user_id.data_ptr(), pos_id.data_ptr(), n, B.ptr(pr), B.ptr(pi),
+        B.ptr(er), B.ptr(ei), int(max_trials), float(margin), int(seed) & ((1 << 64) - 1),
+        int(pair_base), float(grad_scale), loss.data_ptr(), neg.data_ptr(), trials.data_ptr(),
+        B.ptr(grad_user), B.ptr(grad_item), B.ptr(err), B.stream(dev),
+    )
+    _done(rc, "dr_warp_fwd_bwd", own)
+    return loss, neg, trials
+
+
+def warp_candidates(seed: int, pair_base: int, n_pairs: int, max_trials: int,
+                    n_items: int) -> torch.Tensor:
+    """The candidate stream of ``warp_fwd_bwd`` as a CPU int32 tensor
+    [n_pairs, max_trials] (dr_warp_candidates: host only, needs no GPU)."""
+    out = torch.empty((int(n_pairs), int(max_trials)), dtype=torch.int32)
+    rc = B.lib().dr_warp_candidates(int(seed) & ((1 << 64) - 1), int(pair_base), int(n_pairs),
+                                    int(max_trials), int(n_items), out.data_ptr())
+    B.check(rc, "dr_warp_candidates")
+    return out
+
+
 # --------------------------------------------------------------------------- point-wise MSE
 def mse_fwd_bwd(
     user_table: torch.Tensor,

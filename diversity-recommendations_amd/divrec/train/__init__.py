@@ -10,6 +10,7 @@ from .utils import (
     point_wise_train_loop,
     recommendations_score_loop,
     recommendations_train_loop,
+    warp_train_loop,
 )
 
 __all__ = [
@@ -21,6 +22,7 @@ __all__ = [
     "point_wise_train_loop",
     "pair_wise_train_loop",
     "diversity_pair_wise_train_loop",
+    "warp_train_loop",
     "als_train_loop",
     "recommendations_train_loop",
     "fused_adam_step",

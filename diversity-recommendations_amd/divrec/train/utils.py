@@ -29,6 +29,9 @@ Same functions, arguments and return values as the reference. On the hot path:
   two transposed dr_csr_row_sum give the feature tables' gradients. The
   point-wise loops run it through its forward and autograd;
   ``diversity_pair_wise_train_loop`` and ``als_train_loop`` refuse it.
+* ``warp_train_loop`` (not in the reference) trains either model with the
+  WARP ranking loss: per batch of (user, positive) pairs ONE dr_warp_fwd_bwd,
+  which draws each pair's negatives until one violates the margin.
 """
 from __future__ import annotations
 
@@ -46,6 +49,7 @@ from divrec.datasets import (
     UserItemInteractionsDataset,
     interaction_csr,
 )
+from divrec.datasets.base_datasets import _device_csr
 from divrec.losses import (
     EmbeddingDistance,
     IntraListDiversityScore,
@@ -54,6 +58,7 @@ from divrec.losses import (
     PairWiseLoss,
     PointWiseLoss,
     RecommendationsAwareLoss,
+    WARPLoss,
 )
 from divrec.metrics import AUCScore
 from divrec.metrics import _rank
@@ -497,19 +502,37 @@ def _composed_grads(model: FeatureMatrixFactorization, U: torch.Tensor, I: torch
     return bufs
 
 
-def _feature_pair_wise_batch(model: FeatureMatrixFactorization, scores, batch, epoch_err):
-    """One batch of the fused FeatureMatrixFactorization + BPR step, up to the
-    optimizer step: (1) compose both tables WHOLE (two dr_csr_row_sum), like
-    the reference's dense Adam over whole tables; (2) ONE dr_bpr_fwd_bwd over
-    the composed tables into the two composed-gradient buffers; (3) two
-    dr_csr_row_sum over the transposed maps into the feature tables' ``.grad``
-    (no atomics: given the composed gradients, bitwise reproducible).
-    Bytes per step beyond dr_bpr_fwd_bwd's own, with nnz the maps' entries, R
+def _feature_fused_step(model: FeatureMatrixFactorization, kernel):
+    """The fused FeatureMatrixFactorization step around a step kernel, up to
+    the optimizer step: (1) compose both tables WHOLE (two dr_csr_row_sum),
+    like the reference's dense Adam over whole tables; (2)
+    ``kernel(U, I, gU, gI)``: ONE step kernel (dr_bpr_fwd_bwd,
+    dr_warp_fwd_bwd) over the composed tables into the two composed-gradient
+    buffers; (3) two dr_csr_row_sum over the transposed maps into the feature
+    tables' ``.grad`` (no atomics: given the composed gradients, bitwise
+    reproducible). Returns what ``kernel`` returns.
+    Bytes per step beyond the kernel's own, with nnz the maps' entries, R
     = no_users + no_items rows and F = Fu + Fi features, all times 4 d:
     compose reads nnz and writes R; the buffers' zeroing writes R; the
     transposed sums read nnz and write F; so 2 nnz + 2 R + F rows of d floats,
-    whatever the batch touches (a row-subset compose is out of scope).
-    Returns what ``_pair_wise_batch`` returns."""
+    whatever the batch touches (a row-subset compose is out of scope)."""
+    dev = model._device()
+    Wu, Wi = model.user_feature_embeddings.weight, model.item_feature_embeddings.weight
+    with torch.no_grad():
+        U, I = model._tables()
+        gU, gI = _composed_grads(model, U, I)
+        out = kernel(U, I, gU, gI)
+        user_map, item_map = model._maps(dev)
+        for W, g, m in ((Wu, gU, user_map), (Wi, gI, item_map)):
+            grad = m.T.sum(g, check=False)  # columns of a transpose: row numbers, valid
+            W.grad = grad if W.grad is None else W.grad.add_(grad)
+    return out
+
+
+def _feature_pair_wise_batch(model: FeatureMatrixFactorization, scores, batch, epoch_err):
+    """One batch of the fused FeatureMatrixFactorization + BPR step, up to the
+    optimizer step: ``_feature_fused_step`` (its docstring prices it) around
+    ONE dr_bpr_fwd_bwd. Returns what ``_pair_wise_batch`` returns."""
     user_id, pos, neg, _, _, _ = batch
     dev = model._device()
     host = user_id.device.type == "cpu"
@@ -520,17 +543,10 @@ def _feature_pair_wise_batch(model: FeatureMatrixFactorization, scores, batch, e
     ids = tuple(t.to(dev, torch.int64, non_blocking=True) for t in (user_id, pos, neg))
     if not host:
         _device_ids_in_range(ids[0], model.no_users, ids[1:], model.no_items)
-    Wu, Wi = model.user_feature_embeddings.weight, model.item_feature_embeddings.weight
-    with torch.no_grad():
-        U, I = model._tables()
-        gU, gI = _composed_grads(model, U, I)
-        epoch_err = _epoch_counter(epoch_err, dev)
-        B = ids[0].numel()
-        losses_b, hits = ops.bpr_fwd_bwd(U, I, *ids, 1.0 / B, gU, gI, err=epoch_err, check=False)
-        user_map, item_map = model._maps(dev)
-        for W, g, m in ((Wu, gU, user_map), (Wi, gI, item_map)):
-            grad = m.T.sum(g, check=False)  # columns of a transpose: row numbers, valid
-            W.grad = grad if W.grad is None else W.grad.add_(grad)
+    epoch_err = _epoch_counter(epoch_err, dev)
+    B = ids[0].numel()
+    losses_b, hits = _feature_fused_step(model, lambda U, I, gU, gI: ops.bpr_fwd_bwd(
+        U, I, *ids, 1.0 / B, gU, gI, err=epoch_err, check=False))
     loss_value = torch.sum(losses_b, dim=0) / B
     row = [s.reduce_loss_values(hits).double() for s in scores or ()]
     return ids, loss_value.detach(), torch.stack(row) if row else None, epoch_err
@@ -629,6 +645,103 @@ def _pair_wise_epoch_means(batch_losses, batch_scores, n_scores) -> Tuple[float,
         rows = torch.stack(batch_scores).double().cpu().tolist()
         means = [sum(r[i] for r in rows) / count for i in range(n_scores)]
     return mean_loss, means
+
+
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z: int) -> int:
+    """splitmix64 finaliser on a Python int (csrc/common.h mix64)."""
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def warp_batch_seed(seed: int, epoch: int, batch: int) -> int:
+    """The uint64 seed warp_train_loop gives batch ``batch`` of epoch ``epoch``."""
+    z = _mix64((int(seed) + 0x9E3779B97F4A7C15 * (int(epoch) + 1)) & _M64)
+    return _mix64(z ^ ((0xD1B54A32D192ED03 * (int(batch) + 1)) & _M64))
+
+
+def warp_train_loop(dataset: PointWiseDataset, model: RankingModel, loss: WARPLoss,
+                    optimizer: torch.optim.Optimizer,
+                    frozen: Optional[UserItemInteractionsDataset] = None, seed: int = 0,
+                    **loader_params) -> Tuple[float, dict]:
+    """One epoch of WARP training (not in the reference); returns (mean batch
+    loss, {"mean_trials": draws per pair, "no_violator": share of the pairs
+    that found no violator within ``loss.max_trials`` draws}).
+
+    ``dataset`` is a DevicePointWiseDataset or a PointWiseDataset: each batch's
+    first two columns are its (user, positive) pairs. Each batch is ONE
+    dr_warp_fwd_bwd: per pair, negatives are drawn on the device until one
+    scores above ``positive - loss.margin``; draws of the user's own items
+    (``dataset.data``, as a CSR built once per call) and of its ``frozen``
+    items are skipped but counted; the update is weighted by
+    log((n_items - 1) // draws), 'mean' reduction (grad_scale 1/B). The draws
+    of a batch depend on (``seed``, the dataset's ``epoch`` counter or 0, the
+    batch number) only. Then the optimizer steps as in pair_wise_train_loop:
+    dr_adam_dense for a plain Adam, dr_adam_rows for a plain SparseAdam over
+    the batch's users and its positives and violators, ``optimizer.step()``
+    otherwise. A FeatureMatrixFactorization runs the kernel inside
+    ``_feature_fused_step`` (SparseAdam is refused for it, as in
+    pair_wise_train_loop). Ids outside the tables raise IndexError after the
+    epoch. TypeError for any other model and for a loss that is not a
+    WARPLoss; ValueError when the tables do not cover the interactions."""
+    featured = _feature_scoring(model)
+    if not (featured or isinstance(model, MatrixFactorization)):
+        raise TypeError("warp_train_loop needs a MatrixFactorization or a "
+                        f"FeatureMatrixFactorization model, got {type(model).__name__}")
+    if not isinstance(loss, WARPLoss):
+        raise TypeError(f"warp_train_loop needs a WARPLoss, got {type(loss).__name__}")
+    if featured and isinstance(optimizer, torch.optim.SparseAdam):
+        raise ValueError("warp_train_loop: FeatureMatrixFactorization has dense gradients (a "
+                         "feature gathers every row that holds it); the lazy SparseAdam path is "
+                         "not offered for it, use torch.optim.Adam")
+    n_users, n_items = int(model.no_users), int(model.no_items)
+    for what, data in (("dataset.data", dataset.data), ("frozen", frozen)):
+        if data is not None and (int(data.number_of_users) > n_users
+                                 or int(data.number_of_items) > n_items):
+            raise ValueError(f"the model's tables ({n_users} users, {n_items} items) do not cover "
+                             f"{what} ({int(data.number_of_users)} users, "
+                             f"{int(data.number_of_items)} items)")
+    dev = model._device()
+    positives = _device_csr(dataset.data, n_users, n_items, dev)
+    exclude = None
+    if frozen is not None and frozen.has_interactions() and frozen.interactions.numel():
+        exclude = _device_csr(frozen, n_users, n_items, dev)
+    model.train()
+    adam = _plain_adam(optimizer)
+    lazy = not featured and _plain_sparse_adam(optimizer)
+    epoch = int(getattr(dataset, "epoch", 0))
+    batch_losses, counts = [], []
+    epoch_err = None  # id range errors of the kernel
+    for k, batch in enumerate(dataset.loader(**loader_params)):
+        uid, pid = (torch.as_tensor(t).to(dev, torch.int64, non_blocking=True) for t in batch[:2])
+        B = uid.numel()
+        epoch_err = _epoch_counter(epoch_err, dev)
+
+        def step(U, I, gU, gI, err=epoch_err, batch_seed=warp_batch_seed(seed, epoch, k)):
+            return ops.warp_fwd_bwd(U, I, uid, pid, positives, exclude, loss.max_trials,
+                                    loss.margin, batch_seed, 0, 1.0 / B, gU, gI, err=err,
+                                    check=False)
+
+        if featured:
+            losses_b, neg, trials = _feature_fused_step(model, step)
+        else:
+            U, I = model.user_embeddings.weight, model.item_embeddings.weight
+            _dense_grads(U, I)
+            losses_b, neg, trials = step(U.data, I.data, U.grad, I.grad)
+        valid = trials > 0  # an out-of-range pair made no draw; its rows are not touched
+        _optimizer_step(optimizer, adam, lazy, lambda: {
+            model.user_embeddings.weight: torch.unique(uid[valid]),
+            model.item_embeddings.weight: torch.unique(torch.cat([pid[valid], neg[neg >= 0]]))})
+        batch_losses.append(torch.sum(losses_b, dim=0) / B)
+        counts.append(torch.stack([trials.sum(), (valid & (neg < 0)).sum(), valid.sum()]))
+    _backend.raise_if_out_of_range(epoch_err, "warp_train_loop")
+    mean_loss, _ = _pair_wise_epoch_means(batch_losses, [], 0)
+    n_trials, n_none, n_pairs = torch.stack(counts).sum(dim=0).cpu().tolist()
+    return mean_loss, {"mean_trials": n_trials / max(n_pairs, 1),
+                       "no_violator": n_none / max(n_pairs, 1)}
 
 
 def diversity_pair_wise_train_loop(dataset: PairWiseDataset, model: MatrixFactorization,

@@ -316,6 +316,53 @@ int dr_mse_fwd_bwd(const float* user_table, int64_t n_user_rows, const float* it
                    float grad_scale, float* pred, float* loss, float* grad_user,
                    float* grad_item, int32_t* err, dr_stream_t stream);
 
+/* WARP step (Weston, Bengio, Usunier 2011, as LightFM implements it; not in
+ * the reference). For pair b = (u, p), with s_p = <U[u], I[p]> in fp32:
+ *   for trial t = 0 .. max_trials-1, in this order:
+ *     c = draw(seed, pair_base + b, 0, t) % n_item_rows   (the counter-based hash
+ *         of dr_sample_pairwise; dr_warp_candidates writes the same stream)
+ *     c == p, c in u's positives row or c in u's exclusion row: the trial is
+ *         used up, nothing is scored (LightFM counts such draws too)
+ *     otherwise s_n = <U[u], I[c]>; s_n > s_p - margin (fp32): c is the
+ *         violator, trials[b] = t + 1, the loop ends
+ *   with a violator: L = log(max(1, (n_item_rows - 1) / trials)), the division
+ *     in integers; loss[b] = L (margin - s_p + s_n), the hinge of this one
+ *     triple evaluated in float64 (the test above is the fp32 one); neg_id[b] = c;
+ *     g = L * grad_scale  (grad_scale = 1/B for the 'mean' reduction)
+ *     grad_user[u] += g (I[c] - I[p]); grad_item[p] -= g U[u]; grad_item[c] += g U[u]
+ *   without one: loss[b] = 0, neg_id[b] = -1, trials[b] = max_trials, no gradient.
+ * The result is defined by trial order alone: it depends on no launch
+ * geometry, and calls on parts of a batch with pair_base = the part's offset
+ * give the whole call's neg_id and trials.
+ * fp32 tables [*, d], d in [1, 512]; ids int64 [B]; the positives and the
+ * exclusions as CSR over the user rows (rowptr int64 [n_user_rows + 1], items
+ * int32 sorted per row), each CSR both pointers or both NULL; max_trials in
+ * [1, 4096]; margin finite; pair_base >= 0; n_item_rows < 2^31 - 1. loss fp32
+ * [B], neg_id int64 [B] and trials int32 [B] may each be NULL. Gradients are
+ * DENSE fp32 tables accumulated with atomics; either may be NULL. A pair with
+ * an out-of-range id reads and adds nothing, gets loss NaN / neg_id -1 /
+ * trials 0 and counts in *err (id range checks, above). batch = 0 is a no-op. */
+int dr_warp_fwd_bwd(const float* user_table, int64_t n_user_rows, const float* item_table,
+                    int64_t n_item_rows, int64_t d, const int64_t* user_id,
+                    const int64_t* pos_id, int64_t batch, const int64_t* pos_rowptr,
+                    const int32_t* pos_items, const int64_t* excl_rowptr,
+                    const int32_t* excl_items, int max_trials, float margin, uint64_t seed,
+                    int64_t pair_base, float grad_scale, float* loss, int64_t* neg_id,
+                    int32_t* trials, float* grad_user, float* grad_item, int32_t* err,
+                    dr_stream_t stream);
+
+/* The candidate stream of dr_warp_fwd_bwd, on the HOST (no HIP call):
+ * out[b * max_trials + t] = draw(seed, pair_base + b, 0, t) % n_items for
+ * b < n_pairs, t < max_trials, int32 in host memory. 1 <= n_items < 2^31 - 1.
+ * For tests and baselines that restate the step outside the kernel. */
+int dr_warp_candidates(uint64_t seed, int64_t pair_base, int64_t n_pairs, int max_trials,
+                       int64_t n_items, int32_t* out);
+
+/* Candidate rows dr_warp_fwd_bwd keeps in flight per round after a pair's
+ * first in this build (a compile-time choice that changes no result;
+ * DESIGN.md §3.6c). */
+int dr_warp_round(void);
+
 /* Dense Adam step in fp32 over n elements, the update torch.optim.Adam
  * (amsgrad=False, maximize=False) applies at divrec/train/utils.py:151:
  *   g = grad + weight_decay * param; m = lerp(m, g, 1 - beta1);
