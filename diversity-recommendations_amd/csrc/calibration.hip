@@ -33,13 +33,7 @@ constexpr int kMaxC = kPer * 64;          // 1024
 constexpr int kMaxG = DR_CALIB_MAX_LABELS;
 static_assert(kMaxG == 64, "one lane per category");
 
-// Lane g's entry of the normalised profile row: max(w_g, 0) / sum (NaN counts
-// as 0; 0 everywhere for a row without positive weight).
-__device__ __forceinline__ float profile_entry(const float* __restrict__ row, int G, int lane) {
-  const float w = fmaxf(lane < G ? row[lane] : 0.f, 0.f);
-  const float sum = dr::wave_sum_dpp_f32(w);
-  return sum > 0.f ? w / sum : 0.f;
-}
+using dr::profile_entry;  // lane g's entry of the normalised profile row
 
 // p log(p / q~) with q~ = (1 - alpha) share + alpha p (>= alpha p, so finite); 0 where p = 0
 __device__ __forceinline__ float kl_term(float p, float logp, float share) {

@@ -100,6 +100,14 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Workgroup barrier that orders LDS traffic only: the wave's LDS operations
+// are waited for (lgkmcnt), its global loads and stores stay in flight.
+// __syncthreads() also waits for those (vmcnt(0)), which puts a store's whole
+// round trip into every step of a loop that stores a result per step.
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
 // v_mfma_f32_32x32x16: accumulator register q of a lane of half-wave h
 // (lane >> 5) holds row tile_row(q, h) of column (lane & 31).
 __host__ __device__ constexpr int tile_row(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
@@ -295,6 +303,14 @@ __device__ __forceinline__ float wave_sum_dpp_f32(float v) {  // uniform: the wa
   v += dpp_f32<0x142, 0xA>(v);
   v += dpp_f32<0x143, 0xC>(v);
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+// Lane g's entry of a normalised profile row (the calibrated and the xQuAD
+// re-rank and their metrics): max(w_g, 0) / sum (NaN counts as 0; 0 everywhere
+// for a row without positive weight). G <= 64; lanes >= G get 0.
+__device__ __forceinline__ float profile_entry(const float* __restrict__ row, int G, int lane) {
+  const float w = fmaxf(lane < G ? row[lane] : 0.f, 0.f);
+  const float sum = wave_sum_dpp_f32(w);
+  return sum > 0.f ? w / sum : 0.f;
 }
 // v[lane] and v[lane ^ 16] / v[lane ^ 32], in an order that depends on the
 // lane's half (v_permlane16/32_swap: one VALU, no LDS round trip): for

@@ -54,9 +54,7 @@ __device__ __forceinline__ float half_swap_max(float x) {
   return fmaxf(r.a, r.b);
 }
 
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
+using dr::lds_barrier;
 // not dr::wait_vmcnt<0>(): hipcc merges the builtin's wait into its own and moves an s_barrier
 __device__ __forceinline__ void wait_dma() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 

@@ -1,5 +1,5 @@
-// Host-side argument checks shared by dr_mmr_rerank, dr_dpp_rerank and
-// dr_calibrated_rerank: each condition, code and message exists once, and an
+// Host-side argument checks shared by dr_mmr_rerank, dr_dpp_rerank,
+// dr_calibrated_rerank and dr_xquad_rerank: each condition, code and message exists once, and an
 // entry point is a short sequence of these calls. A check returns DR_OK, or an
 // error code with dr_last_error() = "<fn>: <message>". Where the entry points
 // answer differently today they keep their answer (pinned by
@@ -27,6 +27,7 @@ struct CandidateRules {
 constexpr CandidateRules kMmrArgs{true, false, kRerankMaxC};
 constexpr CandidateRules kDppArgs{false, false, 128};
 constexpr CandidateRules kCalibratedArgs{false, true, kRerankMaxC};
+constexpr CandidateRules kXquadArgs{false, true, kRerankMaxC};  // answers like kCalibratedArgs
 
 inline int arg_error(const char* fn, int code, const std::string& msg) {
   set_error(std::string(fn) + ": " + msg);
@@ -51,6 +52,22 @@ inline int check_candidates(const char* fn, int64_t n_users, int C, int k_out, f
   if (!(lambda >= 0.f && lambda <= 1.f))  // NaN fails
     return arg_error(fn, DR_EINVAL, "lambda must be in [0, 1]");
   return DR_OK;
+}
+
+// The fp32 item-aspect matrix [n_items, G] of dr_xquad_rerank, dr_aspect_profile
+// and dr_aspect_coverage, and the cells of a user's C x G block in LDS (the
+// re-rank alone; the other two pass C = 0).
+inline int check_aspects(const char* fn, int64_t n_items, int G, int C = 0) {
+  if (G > DR_XQUAD_MAX_ASPECTS) return arg_error(fn, DR_EUNSUPPORTED, "G must be <= 64");
+  if (G < 1 || n_items < 0 || n_items >= 0x7fffffffLL)
+    return arg_error(fn, DR_EINVAL, "G must be >= 1 and n_items in [0, 2^31)");
+  if ((int64_t)C * G > DR_XQUAD_MAX_CELLS)
+    return arg_error(fn, DR_EUNSUPPORTED, "C * G must be <= 32768");
+  return DR_OK;
+}
+// once there are users, rows or lists: no aspect row an id could name
+inline int check_aspects_filled(const char* fn, int64_t n_items) {
+  return n_items == 0 ? arg_error(fn, DR_EINVAL, "empty aspect matrix") : DR_OK;
 }
 
 // The bf16 item table [n_items, d], in three steps: the entry points return

@@ -1,5 +1,6 @@
 from divrec.losses.intra_list_diversity_score import IntraListDiversityScore
 
+from .aspect_coverage_score import AspectCoverageScore, aspect_matrix
 from .auc_score import AUCScore
 from .average_precision_at_k import (
     AveragePrecisionAtKScore,
@@ -15,6 +16,7 @@ from .recall_at_k import RecallAtKScore, recall_at_k
 
 __all__ = [
     "AUCScore",
+    "AspectCoverageScore",
     "AveragePrecisionAtKScore",
     "CalibrationScore",
     "EntropyDiversityScore",
@@ -27,6 +29,7 @@ __all__ = [
     "PRI",
     "PrecisionAtKScore",
     "RecallAtKScore",
+    "aspect_matrix",
     "average_precision_at_k",
     "normalized_discounted_cumulative_gain",
     "precision_at_k",

@@ -23,8 +23,9 @@ or raw pointers, which bump no autograd version, are always seen).
 
 ``recommend_diverse`` composes ``score_topk`` with a diversity re-rank of the
 top candidates (greedy DPP, dr_dpp_rerank, or MMR, dr_mmr_rerank) over the
-bf16 item table, or with the calibrated re-rank over item partition labels
-(dr_calibrated_rerank).
+bf16 item table, with the calibrated re-rank over item partition labels
+(dr_calibrated_rerank), or with the xQuAD re-rank over a multi-hot item-aspect
+matrix (dr_xquad_rerank).
 """
 from __future__ import annotations
 
@@ -37,8 +38,9 @@ from divrec import ops
 from .base_models import RankingModel
 
 PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16}
-RERANKERS = ("dpp", "mmr", "calibrated")  # recommend_diverse methods
-MAX_RERANK_CANDIDATES = 1024  # C of dr_dpp_rerank / dr_mmr_rerank / dr_calibrated_rerank
+RERANKERS = ("dpp", "mmr", "calibrated", "xquad")  # recommend_diverse methods
+# C of dr_dpp_rerank / dr_mmr_rerank / dr_calibrated_rerank / dr_xquad_rerank
+MAX_RERANK_CANDIDATES = 1024
 
 
 class _GatherDot(torch.autograd.Function):
@@ -200,6 +202,8 @@ class _TableModel(RankingModel):
         item_labels: Optional[torch.Tensor] = None,
         user_profile: Optional[torch.Tensor] = None,
         n_labels: Optional[int] = None,
+        item_aspects: Optional[torch.Tensor] = None,
+        aspect_profile: Optional[torch.Tensor] = None,
         user_vectors: Optional[torch.Tensor] = None,
         item_vectors: Optional[torch.Tensor] = None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -211,7 +215,13 @@ class _TableModel(RankingModel):
         (``ops.calibrated_rerank``), which needs ``item_labels`` (int [catalog],
         values in [0, G)) and ``user_profile`` (fp32 [n, G], one row per
         listed user, e.g. ``ops.label_profile`` of the users' history;
-        ``n_labels``, when given, must equal G <= 64) and uses no item rows.
+        ``n_labels``, when given, must equal G <= 64) and uses no item rows,
+        or by "xquad" (``ops.xquad_rerank``), which needs ``item_aspects``
+        (fp32 [catalog, G], G <= 64: the items' aspect memberships in [0, 1])
+        and ``aspect_profile`` (fp32 [n, G], one row per listed user, e.g.
+        ``ops.aspect_profile`` of the users' history), with ``candidates * G
+        <= ops.XQUAD_MAX_CELLS``; there ``lam`` weights relevance as for every
+        method (the xQuAD paper's lambda is ``1 - lam``).
         ``user_vectors`` (fp32 [n, embedding_dim], e.g. ``fold_in_users``)
         replaces the model's users as in ``score_topk``; ``user_ids`` must
         then be None; ``item_vectors`` (fp32 [n, embedding_dim]) replaces the
@@ -250,6 +260,28 @@ class _TableModel(RankingModel):
         elif item_labels is not None or user_profile is not None or n_labels is not None:
             raise ValueError(f'item_labels, user_profile and n_labels belong to method '
                              f'"calibrated", not {method!r}')
+        if method == "xquad":
+            if item_aspects is None or aspect_profile is None:
+                raise ValueError('method "xquad" needs item_aspects and aspect_profile')
+            n_lists = self.no_users if user_ids is None else len(user_ids)
+            if user_vectors is not None:
+                n_lists = len(user_vectors)
+            if item_aspects.dim() != 2 or item_aspects.size(0) < catalog:
+                raise ValueError(f"item_aspects must be [catalog, n_aspects] with a row for each "
+                                 f"of the {catalog} items, got {tuple(item_aspects.shape)}")
+            G = item_aspects.size(1)
+            if not 1 <= G <= ops.XQUAD_MAX_ASPECTS:
+                raise ValueError(f"need 1 <= n_aspects <= {ops.XQUAD_MAX_ASPECTS}, got {G}")
+            if aspect_profile.dim() != 2 or tuple(aspect_profile.shape) != (n_lists, G):
+                raise ValueError(f"aspect_profile must be [{n_lists}, {G}], one row per user, "
+                                 f"got {tuple(aspect_profile.shape)}")
+            if candidates * G > ops.XQUAD_MAX_CELLS:
+                raise ValueError(f"candidates * n_aspects = {candidates} * {G} exceeds "
+                                 f"{ops.XQUAD_MAX_CELLS}: at most "
+                                 f"{ops.XQUAD_MAX_CELLS // G} candidates fit with {G} aspects")
+        elif item_aspects is not None or aspect_profile is not None:
+            raise ValueError(f'item_aspects and aspect_profile belong to method "xquad", '
+                             f'not {method!r}')
         cand, cand_scores = self.score_topk(candidates, user_ids=user_ids, exclude=exclude,
                                             precision=precision, n_items=n_items,
                                             user_vectors=user_vectors, item_vectors=item_vectors)
@@ -259,6 +291,11 @@ class _TableModel(RankingModel):
             picks, _ = ops.calibrated_rerank(
                 cand32, cand_scores, item_labels[:catalog].to(dev),
                 user_profile.to(dev, torch.float32), k, lam)
+        elif method == "xquad":
+            dev = cand.device
+            picks, _ = ops.xquad_rerank(
+                cand32, cand_scores, item_aspects[:catalog].to(dev, torch.float32),
+                aspect_profile.to(dev, torch.float32), k, lam)
         else:
             rows = self._scan_sides("bf16", None, item_vectors, users=False)[1][:catalog]
             if method == "dpp":

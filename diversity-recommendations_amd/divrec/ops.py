@@ -931,6 +931,115 @@ def calibration_kl(recs: torch.Tensor, item_labels: torch.Tensor, profile: torch
     return out
 
 
+# --------------------------------------------------------------------------- xQuAD
+XQUAD_MAX_ASPECTS = 64   # DR_XQUAD_MAX_ASPECTS
+XQUAD_MAX_CELLS = 32768  # DR_XQUAD_MAX_CELLS: candidates x aspects of one user in LDS
+
+
+def _aspects(item_aspects: torch.Tensor) -> torch.Tensor:
+    _need(item_aspects.dtype == torch.float32 and item_aspects.dim() == 2,
+          "item aspects must be fp32 [n_items, n_aspects]")
+    _need(item_aspects.size(0) >= 1, "item aspects must not be empty")
+    _need(1 <= item_aspects.size(1) <= XQUAD_MAX_ASPECTS,
+          f"n_aspects must be in [1, {XQUAD_MAX_ASPECTS}]")
+    return item_aspects.contiguous()
+
+
+def _aspect_profile(profile: torch.Tensor, n: int, G: int) -> torch.Tensor:
+    _need(profile.dtype == torch.float32 and profile.dim() == 2 and profile.size(0) == n
+          and profile.size(1) == G, "aspect profile must be fp32 [n, n_aspects]")
+    return profile.contiguous()
+
+
+def xquad_rerank(
+    cand_items: torch.Tensor, cand_scores: torch.Tensor, item_aspects: torch.Tensor,
+    aspect_profile: torch.Tensor, k_out: int, lam: float = 0.5,
+    err: Optional[torch.Tensor] = None, check: bool = True,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Greedy xQuAD re-rank (Santos et al. 2010) over per-user candidates (int32
+    [n, C] + fp32 [n, C]) -> (items int32 [n, k_out], cov fp32 [n, k_out]): each
+    pick maximises lam * score + (1 - lam) * sum_a m_a c_a, c the candidate's
+    row of ``item_aspects`` (fp32 [n_items, G], G <= 64, values clamped to
+    [0, 1]) and m the mass of the normalised row of ``aspect_profile`` (fp32
+    [n, G], e.g. ``aspect_profile`` of the user's history) that the list has
+    not covered yet (include/divrec_hip.h). ``lam`` weights relevance: the
+    paper's lambda is 1 - lam. ``cov[:, t]`` is the list's expected aspect
+    coverage after pick t, so ``cov[:, -1]`` is ``aspect_coverage`` of the
+    finished list. A list that runs out of live candidates ends in -1 with the
+    coverage repeated. ``C * G <= XQUAD_MAX_CELLS``. Candidate ids < 0 are
+    empty slots; a candidate id past the matrix is never picked and counted:
+    into the caller's ``err`` (an int32 device counter) when given, else with
+    ``check`` the call reads the count (one sync) and raises IndexError."""
+    dev = B.require_device(cand_items, cand_scores, item_aspects, aspect_profile, err)
+    cand_items, cand_scores, n, C = _candidates(cand_items, cand_scores)
+    aspects = _aspects(item_aspects)
+    profile = _aspect_profile(aspect_profile, n, aspects.size(1))
+    out = torch.empty((n, int(k_out)), dtype=torch.int32, device=dev)
+    cov = torch.empty((n, int(k_out)), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out, cov
+    err, own = _counter(dev, err, check)
+    rc = B.lib().dr_xquad_rerank(
+        cand_items.data_ptr(), cand_scores.data_ptr(), n, C,
+        aspects.data_ptr(), aspects.size(0), aspects.size(1), profile.data_ptr(), int(k_out),
+        float(lam), out.data_ptr(), cov.data_ptr(), B.ptr(err), B.stream(dev),
+    )
+    _done(rc, "dr_xquad_rerank", own)
+    return out, cov
+
+
+def aspect_profile(rowptr: torch.Tensor, items: torch.Tensor, item_aspects: torch.Tensor,
+                   err: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:
+    """fp32 [n, G]: the normalised aspect sums of every row of the CSR (rowptr
+    int64 [n + 1], items int32) over ``item_aspects`` (fp32 [n_items, G]), the
+    profile ``xquad_rerank`` and ``aspect_coverage`` take; an empty or all-zero
+    row is a zero row. An item outside the matrix is skipped and counted, into
+    ``err`` when given, else with ``check`` it raises IndexError (one counter
+    read). Bitwise reproducible (no atomics)."""
+    dev = B.require_device(rowptr, items, item_aspects, err)
+    _need(rowptr.dtype == torch.int64 and rowptr.dim() == 1 and rowptr.numel() >= 1,
+          "rowptr int64 [n + 1]")
+    _need(items.dtype == torch.int32 and items.dim() == 1, "items must be int32 1-D")
+    aspects = _aspects(item_aspects)
+    n, G = rowptr.numel() - 1, aspects.size(1)
+    out = torch.empty((n, G), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    err, own = _counter(dev, err, check)
+    rc = B.lib().dr_aspect_profile(
+        rowptr.contiguous().data_ptr(), items.contiguous().data_ptr() if items.numel() else None,
+        n, aspects.data_ptr(), aspects.size(0), G, out.data_ptr(), B.ptr(err), B.stream(dev),
+    )
+    _done(rc, "dr_aspect_profile", own)
+    return out
+
+
+def aspect_coverage(recs: torch.Tensor, item_aspects: torch.Tensor, aspect_profile: torch.Tensor,
+                    err: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:
+    """fp32 [n]: the expected aspect coverage sum_a p_a (1 - prod_j (1 - c_{j,a}))
+    of each list of ``recs`` [n, k] (int32 or int64; entries < 0, the tail of a
+    list that ended early, are skipped) under the normalised rows p of
+    ``aspect_profile`` (fp32 [n, G]); 1 is a list that covers every aspect the
+    profile weighs, and with a uniform profile and binary aspects it is
+    subtopic recall. An entry past the matrix is skipped and counted, into
+    ``err`` when given, else with ``check`` it raises IndexError."""
+    dev = B.require_device(recs, item_aspects, aspect_profile, err)
+    recs, rc_dt = _recs(recs)
+    n, k = recs.shape
+    aspects = _aspects(item_aspects)
+    profile = _aspect_profile(aspect_profile, n, aspects.size(1))
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    err, own = _counter(dev, err, check)
+    rc = B.lib().dr_aspect_coverage(
+        recs.data_ptr() if k else None, rc_dt, n, k, aspects.data_ptr(), aspects.size(0),
+        aspects.size(1), profile.data_ptr(), out.data_ptr(), B.ptr(err), B.stream(dev),
+    )
+    _done(rc, "dr_aspect_coverage", own)
+    return out
+
+
 # --------------------------------------------------------------------------- rank metrics
 def rank_metrics(
     recs: torch.Tensor, pos_rowptr: torch.Tensor, pos_items: torch.Tensor

@@ -35,7 +35,7 @@ Same functions, arguments and return values as the reference. On the hot path:
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -62,6 +62,7 @@ from divrec.losses import (
 )
 from divrec.metrics import AUCScore
 from divrec.metrics import _rank
+from divrec.metrics.aspect_coverage_score import aspect_matrix
 from divrec.metrics.calibration_score import partition_labels
 from divrec.models import FeatureMatrixFactorization, MatrixFactorization, RankingModel
 from divrec.models.matrix_factorization import MAX_RERANK_CANDIDATES, RERANKERS
@@ -267,7 +268,9 @@ def get_model_recommendations(dataset: RankingDataset, model: RankingModel,
 def get_diverse_recommendations(dataset: RankingDataset, model: RankingModel,
                                 number_of_recommendations: int, candidates: int,
                                 method: str = "dpp", lam: float = 0.5,
-                                items_partition_feature: str = "partition") -> torch.LongTensor:
+                                items_partition_feature: str = "partition",
+                                items_aspect_features: Optional[Sequence[str]] = None,
+                                ) -> torch.LongTensor:
     """Diversity re-ranked lists of every user of ``dataset`` (LongTensor
     [U, k] on the CPU, not in the reference): the top-``candidates``
     candidates of ``get_model_recommendations``' scan (fp32 scores, frozen
@@ -278,11 +281,17 @@ def get_diverse_recommendations(dataset: RankingDataset, model: RankingModel,
     ``dataset.data.item_features[items_partition_feature]`` (at most 64 of
     them), the user's profile the label histogram of its ``frozen`` items, its
     history (``ops.label_profile`` over ``dataset.exclusion_csr()``).
+    ``method`` "xquad" re-ranks for coverage of the aspects a user's history
+    weighs: the item-aspect matrix is the ``dataset.data.item_features``
+    columns named by ``items_aspect_features`` (at most 64, e.g. the genre
+    columns of ML-100K; ``candidates`` times their count at most
+    ``ops.XQUAD_MAX_CELLS``), the user's profile the aspect shares of its
+    ``frozen`` items (``ops.aspect_profile`` over the same CSR).
     A FeatureMatrixFactorization is served like a MatrixFactorization.
     ValueError for a model outside the MF fast path, for ragged candidate
     lists (as ``get_model_recommendations``), for a list that ends early
-    (fewer eligible candidates than picks) and, for "calibrated", without
-    ``frozen`` or without the feature."""
+    (fewer eligible candidates than picks) and, for "calibrated" and "xquad",
+    without ``frozen`` or without the feature(s)."""
     k, cands = int(number_of_recommendations), int(candidates)
     if method not in RERANKERS:
         raise ValueError(f"method must be one of {sorted(RERANKERS)}, got {method!r}")
@@ -303,20 +312,37 @@ def get_diverse_recommendations(dataset: RankingDataset, model: RankingModel,
         if excl is None:
             raise ValueError('method "calibrated" takes the users\' profiles from the frozen '
                              'interactions: the dataset has none')
+    aspects = None
+    if method == "xquad":
+        if items_aspect_features is None:
+            raise ValueError('method "xquad" needs items_aspect_features: the item feature '
+                             'columns that form the aspect matrix')
+        aspects = aspect_matrix(dataset.data, items_aspect_features)
+        if excl is None:
+            raise ValueError('method "xquad" takes the users\' profiles from the frozen '
+                             'interactions: the dataset has none')
+    elif items_aspect_features is not None:
+        raise ValueError(f'items_aspect_features belongs to method "xquad", not {method!r}')
     c_len = _list_length(dataset, excl, n_users, n_items, cands)
     if c_len < k:
         raise ValueError(f"a user has {c_len} candidates, fewer than the {k} recommendations asked for")
     user_ids = None if n_users == model.no_users else torch.arange(n_users)
-    calibrated = {}
+    extra = {}  # the keyword arguments of the label- and aspect-aware methods
     if labels is not None:
         dev, n_labels = model._device(), int(labels.max()) + 1
         labels = labels.to(dev)
         # the labels are validated above; a frozen item outside the catalog has none and is skipped
         profile = ops.label_profile(excl[0].to(dev), excl[1].to(dev), labels, n_labels,
                                     check=False)
-        calibrated = dict(item_labels=labels, user_profile=profile)
+        extra = dict(item_labels=labels, user_profile=profile)
+    if aspects is not None:
+        dev = model._device()
+        aspects = aspects.to(dev)
+        # a frozen item outside the catalog has no aspects and is skipped
+        profile = ops.aspect_profile(excl[0].to(dev), excl[1].to(dev), aspects, check=False)
+        extra = dict(item_aspects=aspects, aspect_profile=profile)
     items, _ = model.recommend_diverse(k, c_len, method=method, lam=lam, user_ids=user_ids,
-                                       exclude=excl, n_items=n_items, **calibrated)
+                                       exclude=excl, n_items=n_items, **extra)
     items = items.cpu()
     if bool((items < 0).any()):
         short = int((items < 0).any(dim=1).sum())

@@ -52,7 +52,8 @@ const char* dr_build_id(void);
 const char* dr_last_error(void);
 
 /* Planner knobs: process-wide overrides of dr_score_topk's launch planner (and
- * of dr_mmr_rerank's, dr_dpp_rerank's and dr_calibrated_rerank's grids, DR_KNOB_SCAN_SLOTS), for tests and A/B timing runs
+ * of dr_mmr_rerank's, dr_dpp_rerank's, dr_calibrated_rerank's and
+ * dr_xquad_rerank's grids, DR_KNOB_SCAN_SLOTS), for tests and A/B timing runs
  * only. Every plan gives identical results; only the time differs. The
  * library reads no environment variable: a knob holds the default plan until
  * it is set here, and value NaN restores the default. Thread-safe (atomic). */
@@ -538,6 +539,78 @@ int dr_label_profile(const int64_t* rowptr, const int32_t* items, int64_t n_rows
 int dr_calibration_kl(const void* recs, int rec_dtype, int64_t n_users, int k,
                       const int32_t* item_labels, int64_t n_items, int G, const float* profile,
                       float* out, int32_t* err, dr_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * xQuAD aspect-aware re-rank over a multi-hot item-aspect matrix (Santos,
+ * Macdonald, Ounis, "Exploiting Query Reformulations for Web Search Result
+ * Diversification", WWW 2010; for recommendation: Vargas & Castells, RecSys
+ * 2011; no reference symbol, as for MMR, DPP and the calibrated re-rank; the
+ * aspects are columns of the reference's item_features, e.g. the 19 genre
+ * columns of its ML-100K loader). item_aspects fp32 [n_items, G], row-major;
+ * per user a profile row w[G] (fp32). With
+ *   c_{i,a} = min(max(item_aspects[i, a], 0), 1)         (NaN counts as 0)
+ *   p_a     = max(w_a, 0) / sum_a max(w_a, 0)            (NaN counts as 0; a row
+ *             whose sum is 0 gives p = 0: the rules of dr_calibrated_rerank)
+ * the uncovered mass m_a starts at p_a, and each step picks the live candidate
+ * of highest
+ *   value_i = lambda * score_i + (1 - lambda) * sum_a m_a c_{i,a}
+ * (ties -> lowest candidate position), then m_a <- m_a (1 - c_{pick,a}).
+ * lambda weights RELEVANCE, as in every re-ranker here; the paper's lambda is
+ * 1 - lambda. lambda = 1, a zero profile row and an all-zero aspect matrix
+ * each give the stable order by score exactly (the diversity term is +-0).
+ * cand_items int32 [n_users, C] (ids < 0: empty slots), cand_scores fp32
+ * [n_users, C] (-inf and NaN count as -FLT_MAX), profile fp32 [n_users, G];
+ * out_items int32 [n_users, k_out] in pick order; out_cov fp32 [n_users,
+ * k_out] (may be NULL): the list's coverage after each pick,
+ *   sum_a (p_a - m_a) = sum_a p_a (1 - prod_{j in list} (1 - c_{j,a})),
+ * accumulated from the steps' gains, which telescope: out_cov[:, k_out - 1] is
+ * the finished list's dr_aspect_coverage.
+ * Never live, never picked: ids < 0; ids >= n_items (added to *err, an int32
+ * device counter that may be NULL; their row is never read). When no live
+ * candidate is left the remaining picks are -1 and out_cov repeats. Positions
+ * are picked once each; duplicate ids are not detected.
+ * 1 <= C <= 1024 and 1 <= G <= DR_XQUAD_MAX_ASPECTS, and C * G <=
+ * DR_XQUAD_MAX_CELLS: 128 KiB of fp32, the largest user block that leaves room
+ * beside it in a CU's 160 KiB of LDS (beyond either: DR_EUNSUPPORTED);
+ * 1 <= k_out <= C, lambda in [0, 1]; n_items = 0 with users present is
+ * DR_EINVAL.
+ * Arithmetic (fp32, no fused multiply-add): div_i = sum_a p_a c_{i,a} is summed
+ * once in aspect order; a step forms value_i = lambda s_i + (1 - lambda) div_i,
+ * and for each aspect of the pick with c_{pick,a} != 0, in aspect order:
+ * delta = m_a c_{pick,a}, m_a -= delta, div_i -= delta c_{i,a}, cov += delta.
+ * Launch: one 256-thread workgroup per user at a time with the user's clamped
+ * C x G block aspect-major in LDS, a persistent grid of as many workgroups per
+ * CU as are resident (DR_KNOB_SCAN_SLOTS caps the CUs, as for dr_mmr_rerank). */
+#define DR_XQUAD_MAX_ASPECTS 64
+#define DR_XQUAD_MAX_CELLS 32768
+int dr_xquad_rerank(const int32_t* cand_items, const float* cand_scores, int64_t n_users, int C,
+                    const float* item_aspects, int64_t n_items, int G, const float* profile,
+                    int k_out, float lambda, int32_t* out_items, float* out_cov, int32_t* err,
+                    dr_stream_t stream);
+
+/* Profiles for dr_xquad_rerank from a history CSR (rowptr int64 [n_rows + 1],
+ * items int32; the exclusion CSR of dr_score_topk is one):
+ *   out[r, a] = sum_{i in row r} c_{i,a} / sum_a sum_{i in row r} c_{i,a}
+ * fp32 [n_rows, G]; an empty or all-zero row gives a zero row. Items outside
+ * [0, n_items) are skipped and counted in *err. No atomics: each (row, aspect)
+ * is summed in the row's order by fp32 adds, the denominator is one fixed
+ * tree over the aspects, so the result is bitwise reproducible; for binary
+ * matrices the sums are exact integers (rows of fewer than 2^24 items) and the
+ * value is one fp32 divide. Limits of G and n_items as above. */
+int dr_aspect_profile(const int64_t* rowptr, const int32_t* items, int64_t n_rows,
+                      const float* item_aspects, int64_t n_items, int G, float* out, int32_t* err,
+                      dr_stream_t stream);
+
+/* Expected aspect coverage of finished lists (the objective of dr_xquad_rerank;
+ * subtopic recall, Zhai et al., SIGIR 2003, when p is uniform and the aspects
+ * binary): out[u] = sum_a p_a (1 - prod_{j in recs[u, :]} (1 - c_{j,a})), p the
+ * normalised profile row as above; recs [n_users, k], rec_dtype DR_I32 or
+ * DR_I64. Entries < 0 (a list that ended early) are skipped; entries >=
+ * n_items are skipped and counted in *err. A list without a valid entry
+ * scores 0. */
+int dr_aspect_coverage(const void* recs, int rec_dtype, int64_t n_users, int k,
+                       const float* item_aspects, int64_t n_items, int G, const float* profile,
+                       float* out, int32_t* err, dr_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Implicit-feedback ALS row solve (Hu, Koren, Volinsky, ICDM 2008; no
