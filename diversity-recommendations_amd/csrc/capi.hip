@@ -12,8 +12,8 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 // Knob values, NaN = the default plan. Set only through dr_set_plan_knob: the
 // library reads no environment variable.
 static std::atomic<double> g_knobs[DR_KNOB_COUNT] = {
-    {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}};
-static_assert(DR_KNOB_COUNT == 11, "initialise every knob");
+    {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}, {NAN}};
+static_assert(DR_KNOB_COUNT == 13, "initialise every knob");
 
 // The range of each knob (include/divrec_hip.h): the planner casts integer
 // knobs with (int), so a value outside them would be undefined behaviour.
@@ -28,6 +28,7 @@ static const char* knob_range_error(int knob, double v) {
     case DR_KNOB_SCAN_SEED:
     case DR_KNOB_GUESS_TIGHT:
     case DR_KNOB_ILD_STREAM:
+    case DR_KNOB_SCAN_QUEUE:
       return (v == 0.0 || v == 1.0) ? nullptr : "0 or 1";
     case DR_KNOB_GUESS_Z1:
     case DR_KNOB_GUESS_C1:
@@ -38,6 +39,8 @@ static const char* knob_range_error(int knob, double v) {
                  : "0 (off), 1 (on, the default budget) or a budget in GiB in (1, 2^20]";
     case DR_KNOB_ILD_BUFS:
       return (integral && v >= 1.0 && v <= 64.0) ? nullptr : "an integer in [1, 64]";
+    case DR_KNOB_SCAN_FLOOR:  // rows: one item tile at the least
+      return (integral && v >= 32.0 && v <= 1073741824.0) ? nullptr : "an integer in [32, 2^30]";
     default:
       return "a known knob";
   }

@@ -530,7 +530,9 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
   constexpr int kLpt = S::kLpt, RING_BYTES = S::RING_BYTES, SB = S::SB, WAVE_BYTES = S::WAVE_BYTES;
   constexpr bool kHalf = S::kHalf, M16 = S::M16, kLaneOnce = S::kLaneOnce, STAGED = S::STAGED;
   constexpr bool UTP = S::UTP;
-  __shared__ __attribute__((aligned(16))) char smem[S::LDS_BYTES];
+  // the ring and the waves' areas, then the claimed unit id (unit loop)
+  __shared__ __attribute__((aligned(16))) char smem[S::LDS_BYTES + 16];
+  static_assert(S::LDS_BYTES + 16 <= 163840, "LDS budget");
 
   // A buffer is compacted once it holds more than flush_at keys; a stage adds
   // at most MARGIN keys per user, so flush_at + MARGIN <= CAP. A small gap
@@ -587,7 +589,7 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
   }
   int64_t n_head = a.n_head < n_ublocks ? a.n_head : n_ublocks;
   int tail_chunks = a.tail_chunks;
-  int64_t chunk_items = a.chunk_items, pad_rows = a.n_users_pad;
+  int64_t chunk_items = 0, pad_rows = a.n_users_pad;  // chunk_items: the device-side plan's
   if (a.dev_split > 0) {  // second-tier rescan: every failing block split over the grid
     const DevSplit ds = dev_split_plan(n_ublocks, gridDim.x, a.dev_split, a.buf_blocks, a.n_items,
                                        (int64_t)SR * kTileItems);
@@ -598,7 +600,32 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
   }
   const int64_t n_tail = n_ublocks - n_head;
   const int64_t n_units = n_head + n_tail * tail_chunks;
-  for (int64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+  // Units in id order: head blocks, then the tail chunks, chunk index major
+  // (the longest chunks first). Without a queue workgroup b runs units b,
+  // b + grid, ... With one (TopkArgs::unit_queue) lane 0 claims the next id and
+  // publishes it through unit_word; every wave reads it behind the workgroup
+  // barrier and takes the same branch on it, so the waves leave the loop
+  // together and none is left at a barrier. The word is written again only
+  // after the __syncthreads() that ends the unit, which every wave reaches
+  // after its read.
+  // thread 0, by a scalar and `lane` (live anyway): no VGPR kept for the test
+  const bool wave0 = SEEDED && __builtin_amdgcn_readfirstlane(threadIdx.x) < 64u;
+  for (int64_t unit = blockIdx.x;; unit += gridDim.x) {
+    if constexpr (SEEDED) {  // only the seeded main scan is given a queue
+      if (a.unit_queue != nullptr) {
+        // a zero made here: the word's and the queue's address registers are
+        // then built per claim, not hoisted into VGPRs held across the tile
+        // loop (which has none to spare: a B fragment went to scratch)
+        uint32_t z;
+        asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+        volatile uint32_t* unit_word =
+            reinterpret_cast<volatile uint32_t*>(smem + S::LDS_BYTES + z);
+        if (wave0 && lane == 0) *unit_word = atomicAdd(a.unit_queue + z, 1u);
+        __syncthreads();
+        unit = __builtin_amdgcn_readfirstlane(*unit_word);
+      }
+    }
+    if (unit >= n_units) break;
     DG_T0(t_pro);
     int64_t ub, i_beg = 0, i_end = a.n_items, brow;
     bool chunked = false;  // a tail chunk unit: compacted down to end_keep at its end
@@ -609,8 +636,20 @@ __global__ __launch_bounds__(kWavesScan * 64, kWavesScan / 4) void score_scan_ke
       const int64_t idx = unit - n_head;
       const int64_t j = idx / n_tail, tb = idx % n_tail;
       ub = n_head + tb;
-      i_beg = j * chunk_items;
-      i_end = i_beg + chunk_items < a.n_items ? i_beg + chunk_items : a.n_items;
+      if (a.dev_split > 0) {  // the device-side plan's equal chunks
+        i_beg = j * chunk_items;
+        i_end = i_beg + chunk_items < a.n_items ? i_beg + chunk_items : a.n_items;
+      } else {
+        // The catalog length goes through a VGPR, so the whole rule is computed
+        // in VGPRs (free here: the B fragments are not loaded yet) and only its
+        // result comes back to SGPRs, which the tile loop has none to spare of.
+        uint32_t nv = (uint32_t)a.n_items;  // < 2^31 (check_score_call)
+        asm volatile("" : "+v"(nv));
+        const ChunkRange r = tail_chunk_bounds((int64_t)nv, tail_chunks, SR * kTileItems,
+                                               a.chunk_floor, (int)j);
+        i_beg = uni64(r.beg);
+        i_end = uni64(r.end);
+      }
       brow = j == 0 ? ub * UPWG : pad_rows + ((j - 1) * n_tail + tb) * UPWG;
       chunked = tail_chunks > 1;
     }

@@ -31,6 +31,14 @@ enum {
 // round 6 with PMC FETCH beside the time at the headline (1M x 10M, k = 100;
 // profiles/r06/stage_fetch/): 72 KB 1770 ms, main-scan FETCH 227.6 GB;
 // 64 KB 1776 ms, 243.0 GB. 72 KB wins both.
+// Units (profiles/scan_units/): XCDs differ in speed persistently (1M x 10M:
+// their mean workgroup lifetimes span 1604-1643 ms), so under the static unit
+// loop the mean workgroup idled 27 ms (1.6 %) at the end of the seeded main
+// scan. Its workgroups now claim units from a device queue
+// (TopkArgs::unit_queue) and the tail chunks are graded, longest first
+// (tail_chunk_bounds): idle 6.7 ms; one-process A/B 1535.6 -> 1499.0 ms at the
+// headline (-2.4 %; the queue alone, on equal chunks, 1527.6), 220.8 -> 217.4
+// at 1M x 1.25M, 1974.0 -> 1965.8 at k = 1000, lists identical.
 #ifndef DR_STAGE_BYTES_WIDE
 #define DR_STAGE_BYTES_WIDE 73728  // ring slot for d = 128 (9 tiles: 72 KB)
 #endif
@@ -193,6 +201,58 @@ struct ScanShape {
   static_assert(!UTP || STAGED, "the per-user-tile jobs stage their survivors");
 };
 
+// The c catalog chunks of a split tail block: rows [beg, end) of chunk j.
+// Lengths are whole stages (the last chunk ends at n_items), never increase
+// with j, and cover [0, n_items) once. A chunk takes half of what is left
+// while that is more than an equal share and leaves every later chunk at
+// least floor_items rows; from there on the rest is shared equally, as
+// ceil(rest / chunks left) stages each, a chunk giving way only so that every
+// later one keeps a stage (none is empty unless the catalog has fewer than c
+// stages). c = 6, a floor far below n_items / 32: 1/2, 1/4, 1/8, 1/16, 1/32,
+// 1/32 of the catalog. floor_items >= n_items / c never halves: c equal
+// chunks of ceil(ceil(n_items / c) / stage) stages, Plan::chunk_items, the
+// plan before units were claimed from a queue (DESIGN.md §3.1 "Grid tail").
+// n_items < 2^31 (check_score_call), floor_items <= 2^31.
+struct ChunkRange {
+  int64_t beg, end;
+};
+__host__ __device__ inline ChunkRange tail_chunk_bounds(int64_t n_items, int c, int stage_items,
+                                                        int64_t floor_items, int j) {
+  const uint32_t st = (uint32_t)stage_items;
+  const int S = (int)(((uint32_t)n_items + st - 1) / st);  // stages in the catalog
+  const int F = (int)(((uint32_t)(floor_items < n_items ? floor_items : n_items) + st - 1) / st);
+  int rem = S, pos = 0, len = 0, per = 0;
+  bool spare = false;  // the equal part has a stage for every chunk
+  for (int i = 0; i <= j; ++i) {
+    pos += len;
+    rem -= len;
+    const int left = c - i;
+    if (per == 0) {
+      const int half = rem >> 1;
+      if ((half - 1) * left >= rem) {  // half > ceil(rem / left)
+        // the shortest chunk if the rest were shared equally from here
+        const int rest = rem - half, later = left - 1;
+        const int share = (int)(((uint32_t)rest + (uint32_t)later - 1) / (uint32_t)later);
+        if (rest - (later - 1) * share >= F) {
+          len = half;
+          continue;
+        }
+      }
+      per = (int)(((uint32_t)rem + (uint32_t)left - 1) / (uint32_t)left);
+      per = per > 0 ? per : 1;
+      spare = rem >= left;
+    }
+    const int most = spare ? rem - (left - 1) : rem;
+    len = per < most ? per : most;
+  }
+  ChunkRange r;
+  r.beg = (int64_t)pos * stage_items;
+  r.end = (int64_t)(pos + len) * stage_items;
+  r.beg = r.beg < n_items ? r.beg : n_items;
+  r.end = r.end < n_items ? r.end : n_items;
+  return r;
+}
+
 struct TopkArgs {
   const char* U;  // user table rows: W * 2 bytes each
   const int64_t* user_ids;
@@ -211,10 +271,20 @@ struct TopkArgs {
   // does not leave CUs idle. Chunk 0 of every block uses the user's buffer
   // row = its position; chunk j >= 1 of tail block b uses row n_users_pad +
   // ((j - 1) * n_tail + b - n_head) * UPWG + (position within the block).
+  // The chunks of a tail block are tail_chunk_bounds(n_items, tail_chunks,
+  // stage items, chunk_floor): graded (longest first) where units are claimed
+  // from the queue below, equal (chunk_floor = n_items) everywhere else.
   int64_t n_ublocks;
   int64_t n_head;
   int tail_chunks;
-  int64_t chunk_items;  // multiple of the stage's item count
+  int64_t chunk_items;  // nominal (equal) chunk length: multiple of the stage's item count
+  int64_t chunk_floor;  // no graded chunk is shorter than this many rows
+  // Unit queue (the seeded main scan of dr_score_topk): a zeroed device word
+  // the workgroups claim their unit ids from, in id order, whenever they are
+  // free (atomicAdd), so a CU that runs ahead takes more of the short last
+  // units instead of idling. NULL: workgroup b runs units b, b + grid, ...
+  // Buffers go by unit id either way, so the lists do not depend on it.
+  uint32_t* unit_queue;
   int end_keep;         // tail chunk units compact buffers above this count at their end
   int head_keep;        // whole-catalog units compact buffers above this count at their end (0: none)
   int slack;            // keys a compaction keeps beyond k (kSlack; smaller for sample scans)
@@ -299,7 +369,8 @@ struct Plan {
   int64_t n_users_pad;
   int64_t n_head;       // user blocks scanned whole (one unit each)
   int tail_chunks;      // catalog chunks per tail block (1 = no split)
-  int64_t chunk_items;  // tail chunk length
+  int64_t chunk_items;  // tail chunk length (nominal: the equal chunks' length)
+  int64_t chunk_floor;  // shortest graded chunk (tail_chunk_bounds); n_items: equal chunks
   int end_keep;         // keys a tail chunk buffer keeps at its end (0: no end compaction)
   int head_keep;        // keys a whole-catalog buffer keeps at its end (0: no end compaction)
   int slack, gap;       // compaction slack and flush gap (TopkArgs)

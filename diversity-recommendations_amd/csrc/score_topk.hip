@@ -560,6 +560,7 @@ Plan make_plan(int64_t n_users, int64_t n_items, int w, int k, bool seedable,
   p.tail_chunks = best_c;
   p.chunk_items = best_c > 1
       ? dr::ceil_div(dr::ceil_div(n_items, best_c), stage_items) * stage_items : n_items;
+  p.chunk_floor = n_items;  // equal chunks (grade_tail_chunks)
   p.slack = kSlack;
   // Long lists: once k + kSlack + kFlushGap passes 1024 keys the head finalize
   // sorts 2048 keys anyway, so a buffer may fill to CAP - margin before its
@@ -582,6 +583,36 @@ Plan make_plan(int64_t n_users, int64_t n_items, int w, int k, bool seedable,
   p.cand_bytes = (size_t)p.buf_rows * p.cap * sizeof(uint64_t);
   p.cnt_bytes = al256((size_t)p.buf_rows * sizeof(int32_t));
   return p;
+}
+
+// Graded tail chunks, for a scan whose workgroups claim their units from the
+// queue (TopkArgs::unit_queue) and have more units than workgroups: the c
+// chunks of a tail block halve from the first down to a floor
+// (tail_chunk_bounds) instead of being equal, so the last units claimed are
+// short and the CUs finish close together (1M x 10M: the last 418 of 2022
+// units are 1/32 of the catalog, ~12 ms, instead of 1/6, ~67 ms). Same chunk
+// count, buffer rows and end_keep; Plan::chunk_items stays the nominal equal
+// length. Without the queue a workgroup's units are fixed (b, b + grid, ...):
+// graded chunks would then make the workgroups' sums differ by up to half a
+// catalog pass, so those scans keep equal chunks.
+// The floor: every chunk ends by compacting all its users (~0.9 ms per
+// workgroup), so chunks must stay long against that; never below the 2^16
+// rows of the planner's own minimum chunk. DR_KNOB_SCAN_FLOOR overrides it
+// (tests force one-stage chunks on small catalogs; a value >= n_items / c
+// gives equal chunks). Chosen at 1M x 1.25M, k = 100 (9 rounds, one process,
+// lists identical; profiles/scan_units/ab_shard_1250k.json): chunks of 625K,
+// 312K and 4 x 78K rows 217.4 ms [217.1-217.9] against 220.6 [219.9-221.3] on
+// the queue with six equal chunks of 208K (what a floor of 2^17 gives there)
+// and 220.8 [220.1-222.3] for the static loop. At 1M x 10M (halving down to
+// 312K rows) 1499.0 ms; a floor of 400 000 rows (1/2, 1/4, 1/8, 3 x 1/24)
+// 1500.8, inside the spread.
+constexpr int64_t kChunkFloor = 65536;
+
+void grade_tail_chunks(Plan& p, int64_t n_items) {
+  const int64_t units = p.n_head + (p.n_ublocks - p.n_head) * p.tail_chunks;
+  if (p.tail_chunks <= 1 || units <= p.grid) return;
+  double v;
+  p.chunk_floor = dr::plan_knob(DR_KNOB_SCAN_FLOOR, &v) ? (int64_t)v : kChunkFloor;
 }
 
 // Largest candidate count the finalize of a head / split-tail user gathers.
@@ -765,6 +796,7 @@ struct Layout {
   Plan main;
   SampleScan sample;
   Guess g;
+  bool queued = false;  // the main scan's workgroups claim units from fcnt[3] (TopkArgs::unit_queue)
   size_t cand = 0, cnt = 0, thr = 0, samp = 0, frows = 0, fpos = 0, fthr = 0, fcnt = 0, diag = 0;
   size_t off_thr() const { return cand + cnt; }
   size_t off_samp() const { return off_thr() + 2 * thr; }
@@ -794,6 +826,9 @@ Layout make_layout(int64_t n_users, int64_t n_items, int w, int k) {
     L.fpos = al256((size_t)n_users * sizeof(int64_t));
     L.fthr = al256((size_t)n_users * sizeof(float));
     L.fcnt = 256;
+    // the seeded main scan claims its units from a device queue (A/B knob: 0 = static loop)
+    L.queued = knob_int(DR_KNOB_SCAN_QUEUE, 1) != 0;
+    if (L.queued) grade_tail_chunks(L.main, n_items);
   }
   L.diag = diag_bytes();
   return L;
@@ -911,6 +946,7 @@ TopkArgs args_for(const Plan& p, const void* user_table, const int64_t* user_ids
   a.n_head = p.n_head;
   a.tail_chunks = p.tail_chunks;
   a.chunk_items = p.chunk_items;
+  a.chunk_floor = p.chunk_floor;
   a.end_keep = p.end_keep;
   a.head_keep = p.head_keep;
   a.slack = p.slack;
@@ -1123,6 +1159,40 @@ extern "C" int dr_score_topk_plan(int64_t n_users, int64_t n_items, int dtype, i
   return DR_OK;
 }
 
+// The catalog chunks of a split tail block (tail_chunk_bounds): bounds[0..c],
+// chunk j = rows [bounds[j], bounds[j + 1]).
+extern "C" int dr_tail_chunk_bounds(int64_t n_items, int chunks, int stage_items,
+                                    int64_t floor_items, int64_t* bounds) {
+  DR_CHECK_ARG(n_items >= 1 && n_items < 0x7fffffffLL, "n_items must be in [1, 2^31)");
+  DR_CHECK_ARG(chunks >= 1 && chunks <= kMaxTailChunks, "chunks must be in [1, 16]");
+  DR_CHECK_ARG(stage_items >= kTileItems && stage_items % kTileItems == 0,
+               "stage_items must be whole tiles");
+  DR_CHECK_ARG(floor_items >= 1 && floor_items <= 0x7fffffffLL, "floor_items must be in [1, 2^31)");
+  DR_CHECK_ARG(bounds, "null bounds");
+  for (int j = 0; j < chunks; ++j) {
+    const ChunkRange r = tail_chunk_bounds(n_items, chunks, stage_items, floor_items, j);
+    bounds[j] = r.beg;
+    bounds[j + 1] = r.end;
+  }
+  return DR_OK;
+}
+
+// The chunks the main scan of dr_score_topk gives a tail block for these
+// arguments on the current device (planner knobs included): *n_chunks = c
+// (1: no split tail) and bounds[0..c]; n_bounds >= 17 always suffices.
+extern "C" int dr_score_topk_tail_chunks(int64_t n_users, int64_t n_items, int dtype, int d, int k,
+                                         int64_t* bounds, int n_bounds, int* n_chunks) {
+  DR_CHECK_ARG(n_users > 0 && n_items > 0, "sizes must be positive");
+  DR_CHECK_ARG(k >= 1 && k <= 1024, "k must be in [1, 1024]");
+  const int w = width_for(dtype, d);
+  DR_CHECK_ARG(w > 0 && cap_for(w, k) > 0, "unsupported dtype / d / k");
+  DR_CHECK_ARG(n_items < 0x7fffffffLL, "item ids must fit int32");
+  const Plan p = make_layout(n_users, n_items, w, k).main;
+  DR_CHECK_ARG(bounds && n_chunks && n_bounds > p.tail_chunks, "bounds must hold chunks + 1 values");
+  *n_chunks = p.tail_chunks;
+  return dr_tail_chunk_bounds(n_items, p.tail_chunks, stage_items(w, p.cap), p.chunk_floor, bounds);
+}
+
 // Users the guessed thresholds failed in the last dr_score_topk call that
 // used this workspace with these arguments: out[0] first tier (rescanned from
 // the safe threshold), out[1] second tier (rescanned from -inf). Host query:
@@ -1199,11 +1269,12 @@ extern "C" int dr_score_topk(const void* user_table, const int64_t* user_ids, in
   float* thr2 = two_tier ? (float*)(ws + L.off_thr() + L.thr) : nullptr;
   char* samp = ws + L.off_samp();
   float* fthr = two_tier ? (float*)(ws + L.off_fthr()) : nullptr;
-  // [0] first-tier failures, [1] second-tier, [2] 1 if this call ran two tiers
+  // [0] first-tier failures, [1] second-tier, [2] 1 if this call ran two tiers,
+  // [3] the main scan's unit queue
   int32_t* fcnt = (int32_t*)(ws + L.off_fcnt());
   const FailList fail1{(int64_t*)(ws + L.off_frows()), (int64_t*)(ws + L.off_fpos()), fcnt};
   const FailList fail2{(int64_t*)(ws + L.off_frows2()), (int64_t*)(ws + L.off_fpos2()), fcnt + 1};
-  DR_CHECK_HIP(hipMemsetAsync(fcnt, 0, 2 * sizeof(int32_t), s));
+  DR_CHECK_HIP(hipMemsetAsync(fcnt, 0, 4 * sizeof(int32_t), s));
   DR_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(fcnt + 2), two_tier ? 1 : 0, 1, s));
   DR_TRY(copy_sample_rows(fn, item_table, L.g.stride, L.g.S, w, samp, s));
   TopkArgs as = sample_args(L.sample, user_table, user_ids, n_users, samp, ws, L.cand);
@@ -1214,7 +1285,9 @@ extern "C" int dr_score_topk(const void* user_table, const int64_t* user_ids, in
   // ---- first tier: the main scan from thr; the finalize lists the users left
   // with fewer than k keys (and their safe thresholds) in fail1
   a.init_thr = thr;
+  a.unit_queue = L.queued ? (uint32_t*)(fcnt + 3) : nullptr;
   DR_TRY(run_scan(fn, p, a, dtype, w, true, s));
+  a.unit_queue = nullptr;  // the rescans below run the static unit loop
   FinalizeArgs verify = fin;
   verify.fail_cnt = fail1.cnt;
   verify.fail_rows = fail1.rows;

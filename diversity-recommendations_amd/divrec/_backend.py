@@ -53,6 +53,8 @@ SIGNATURES = {
         [_p, _p, _i64, _p, _i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _sz, _p],
     ),
     "dr_score_topk_plan": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _i32]),
+    "dr_score_topk_tail_chunks": (_i32, [_i64, _i64, _i32, _i32, _i32, _p, _i32, _p]),
+    "dr_tail_chunk_bounds": (_i32, [_i64, _i32, _i32, _i64, _p]),
     "dr_score_topk_fail_counts": (_i32, [_p, _i64, _i64, _i32, _i32, _i32, _p]),
     "dr_score_topk_seeded_workspace": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "dr_score_topk_seeded": (
@@ -219,7 +221,7 @@ def dtype_code(dt: torch.dtype) -> int:
 PLAN_KNOBS = {
     "scan_slots": 0, "scan_split": 1, "tail_keys": 2, "scan_seed": 3,
     "guess_stride": 4, "guess_z1": 5, "guess_c1": 6, "guess_tight": 7, "sample_dense": 8,
-    "ild_stream": 9, "ild_bufs": 10,
+    "ild_stream": 9, "ild_bufs": 10, "scan_floor": 11, "scan_queue": 12,
 }
 
 

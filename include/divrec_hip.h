@@ -69,7 +69,9 @@ enum dr_plan_knob {
   DR_KNOB_SAMPLE_DENSE = 8, /* 0: sample scan on compacted key buffers, not dense tile maxima; >1: budget GiB */
   DR_KNOB_ILD_STREAM = 9,   /* dr_ild_embedding, k <= 128: 0 = one wave per user, 1 = streamed persistent grid (default: streamed for d = 128 cosine / dot, k > 40) */
   DR_KNOB_ILD_BUFS = 10,    /* streamed ILD: ring slots (1-KB row pieces) per wave, at least one list's (default: as many as LDS allows) */
-  DR_KNOB_COUNT = 11
+  DR_KNOB_SCAN_FLOOR = 11,  /* rows of the shortest graded tail chunk of dr_score_topk's seeded main scan (default 2^16; a value >= items / chunks: equal chunks) */
+  DR_KNOB_SCAN_QUEUE = 12,  /* 0: the seeded main scan runs the static unit loop on equal tail chunks (no device unit queue) */
+  DR_KNOB_COUNT = 13
 };
 /* Set knob `knob` to `value` (NaN = default). DR_EINVAL for an unknown knob,
  * an infinite value or one outside the knob's range: SCAN_SLOTS, SCAN_SPLIT,
@@ -77,7 +79,8 @@ enum dr_plan_knob {
  * and ILD_STREAM 0 or 1; GUESS_Z1 / GUESS_C1 any finite value in [-64, 64];
  * SAMPLE_DENSE 0 (off), 1 (on, the default budget) or a budget in GiB above
  * 1 (up to 2^20); ILD_BUFS an
- * integer in [1, 64]. */
+ * integer in [1, 64]; SCAN_FLOOR an integer in [32, 2^30] (one item tile at
+ * the least); SCAN_QUEUE 0 or 1. */
 int dr_set_plan_knob(int knob, double value);
 /* Current value of a knob (NaN = default; NaN for an unknown knob). */
 double dr_get_plan_knob(int knob);
@@ -167,6 +170,21 @@ int dr_score_topk(const void* user_table, const int64_t* user_ids, int64_t n_use
  * out[12] = the first-tier rank ks1 <= ks the main scan starts from. n_out >= 12. */
 int dr_score_topk_plan(int64_t n_users, int64_t n_items, int dtype, int d, int k, int64_t* out,
                        int n_out);
+
+/* The catalog chunks the main scan of dr_score_topk gives each tail block for
+ * these arguments (host-only query, knobs included): *n_chunks = c (out[3] of
+ * dr_score_topk_plan) and bounds[0..c] (host int64), chunk j = rows
+ * [bounds[j], bounds[j + 1]). Where the scan's workgroups claim their units
+ * from a device queue (the seeded main scan) the chunks are graded, longest
+ * first; else they are equal. n_bounds > c (17 always suffices).
+ * dr_tail_chunk_bounds is the rule itself: c chunks of whole stages of
+ * stage_items rows (whole 32-row tiles) over n_items < 2^31 rows, halving from
+ * the first until a chunk would fall below floor_items (in [1, 2^31)), the
+ * rest equal; floor_items >= n_items / c gives c equal chunks. c in [1, 16]. */
+int dr_score_topk_tail_chunks(int64_t n_users, int64_t n_items, int dtype, int d, int k,
+                              int64_t* bounds, int n_bounds, int* n_chunks);
+int dr_tail_chunk_bounds(int64_t n_items, int chunks, int stage_items, int64_t floor_items,
+                         int64_t* bounds);
 
 /* Guess statistics of the last dr_score_topk call on `workspace` with these
  * arguments (host query; synchronises with a copy): out[0] = users whose

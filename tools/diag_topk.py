@@ -6,6 +6,9 @@
 Loads divrec/_lib/libdivrec_hip_diag.so (built with -DDR_TOPK_DIAG: s_memtime
 stamps around each phase of the scan) and prints per-wave cycle shares. The
 stamps fence the pipeline, so read the SHARES, not the absolute time.
+`workgroup_lifetime_ms` is the unit-loop lifetime of every workgroup of the
+main scan (min / median / max / max - mean over the grid and by workgroup % 8,
+the XCD): max - mean is the time the mean CU idles at the end of the dispatch.
 """
 import argparse
 import json
@@ -91,7 +94,30 @@ def main():
         res[name].update({nm: round(t[14 + i] / max(1.0, t[0]), 4) for i, nm in enumerate(BOUNDARY)})
         res[name]["cycles_per_stage"] = {nm: round(t[14 + i] / max(1.0, t[12]), 1)
                                          for i, nm in enumerate(BOUNDARY)}
+    res["workgroup_lifetime_ms"] = lifetimes(recs)
     print(json.dumps(res))
+
+
+def spread(ms):
+    """min / median / max / max - mean of a list of lifetimes (ms)."""
+    ms = sorted(ms)
+    n = len(ms)
+    mean = sum(ms) / n
+    med = ms[n // 2] if n % 2 else 0.5 * (ms[n // 2 - 1] + ms[n // 2])
+    return {"n": n, "min": round(ms[0], 3), "median": round(med, 3), "max": round(ms[-1], 3),
+            "mean": round(mean, 3), "max_minus_mean": round(ms[-1] - mean, 3)}
+
+
+def lifetimes(recs):
+    """Unit-loop lifetime of every workgroup (its longest wave, s_memrealtime
+    ticks of 10 ns) over the grid, and split by workgroup % 8: the XCD under
+    round-robin placement. The dispatch ends with the slowest workgroup, so
+    max - mean is the time the mean CU runs nothing at the end of the scan."""
+    rt = SLOTS.index("realtime_100mhz")
+    wg = [max(r[rt] for r in recs[g * 8:(g + 1) * 8]) * 1e-5 for g in range(len(recs) // 8)]
+    out = {"grid": spread(wg)}
+    out["by_xcd"] = {str(x): spread(wg[x::8]) for x in range(8) if wg[x::8]}
+    return out
 
 
 if __name__ == "__main__":
