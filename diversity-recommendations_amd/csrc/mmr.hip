@@ -2,7 +2,9 @@
 // -> k_out picks per user. There is no reference symbol; the spec is the
 // build's own:
 //   pick_t = argmax_{i not picked} lambda * s_i - (1 - lambda) * max_{j picked} cos(e_i, e_j)
-// (the max term is 0 before the first pick; ties -> lowest candidate position).
+// (the max term is 0 before the first pick; ties -> lowest candidate position). A live candidate's
+// score is max(s, -FLT_MAX), NaN counting as -FLT_MAX; a row whose sum of squares is 0 has cosine 0
+// with every row and stays eligible on its score.
 //
 // Probe-batch design, one 512-thread workgroup per CU looping over users
 // (persistent grid). MFMA work is proportional to the picks, not to the probes:
@@ -28,6 +30,8 @@
 // mmr_pick_kernel, at the end of the namespace, is the skeleton; each phase is a function above it:
 //   per user:  load_candidates, prefetch_ids, first_pick, prefetch_rows
 //   per batch: select_probes, stage_probes, gram_tile, fast_rounds, fold (forced pick: stage_pick0, fold)
+
+#include <float.h>
 
 #include "common.h"
 #include "rerank_args.h"
@@ -159,8 +163,9 @@ __device__ __forceinline__ void prefetch_rows(const Lane& l, const __bf16* E, in
 }
 
 // ---- candidate rows of user u -> B fragments brow (tile 0 from the prefetch, if any), pen = -inf;
-// ids -> s_citem, scores -> s_cscore, 1/|e| -> s_cinv; out-of-range ids counted into *err and
-// treated as empty. Returns the lane's live mask (bit j: tile j holds a candidate).
+// ids -> s_citem, scores (clamped to -FLT_MAX) -> s_cscore, 1/|e| (0 for a zero row) -> s_cinv;
+// out-of-range ids counted into *err and treated as empty. Returns the lane's live mask (bit j:
+// tile j holds a candidate).
 template <int D>
 __device__ __forceinline__ uint32_t load_candidates(
     const Lane& l, const int32_t* cand_items, const float* cand_scores, const __bf16* E, int C,
@@ -180,7 +185,10 @@ __device__ __forceinline__ uint32_t load_candidates(
     const float sc = ok ? (pre ? s_nscore[c] : cand_scores[u * C + c]) : 0.f;
     if (l.h == 0) {
       s_citem[c] = item;
-      s_cscore[l.cidx(j)] = sc;
+      // a live candidate's value stays above -inf, the key of a dead slot (kDead): -inf and NaN
+      // scores count as -FLT_MAX. Clamped here and not at the load: around the load hipcc merges
+      // the two sources (prefetch image, global) into one flat load
+      s_cscore[l.cidx(j)] = fmaxf(sc, -FLT_MAX);
     }
     pen[j] = -INFINITY;
     if (j == 0 && pre) {
@@ -209,7 +217,9 @@ __device__ __forceinline__ uint32_t load_candidates(
       }
     }
     nsq += __shfl_xor(nsq, 32);
-    if (l.h == 0) s_cinv[l.cidx(j)] = 1.f / sqrtf(nsq);
+    // a zero row: 1/|e| = 0, as for an empty probe slot, so its cosine with every row is 0 (not
+    // 0 * inf = NaN, which the fold's max would drop and leave the max term at -inf)
+    if (l.h == 0) s_cinv[l.cidx(j)] = nsq > 0.f ? 1.f / sqrtf(nsq) : 0.f;
   }
   return live;
 }

@@ -770,7 +770,10 @@ def mmr_rerank(
     Candidate ids < 0 are empty slots; with ``check`` an id >= the table's row
     count raises IndexError after the call (one counter read), as indexing the
     table would (without it such candidates are silently never picked).
-    Widths other than 64 / 128 are zero-padded per call (no cache, so every
+    -inf and NaN scores count as -FLT_MAX (such a candidate stays live and is
+    picked last); an all-zero item row has cosine 0 with every row and stays
+    eligible on its score; +inf scores and non-finite rows are outside the
+    contract. Widths other than 64 / 128 are zero-padded per call (no cache, so every
     write to the table is seen; pass a pre-padded table to avoid the copy)."""
     dev = B.require_device(cand_items, cand_scores, item_table)
     cand_items, cand_scores, n, C = _candidates(cand_items, cand_scores)

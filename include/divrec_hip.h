@@ -456,9 +456,13 @@ int dr_catalog_histogram(const void* recs, int rec_dtype, int64_t n_users, int k
  * MMR diversity re-rank (config 5; no reference symbol — SURVEY.md §8a a16):
  * per user, greedily pick k_out of the C candidates maximising
  *   lambda * score_i - (1 - lambda) * max_{j in S} cos(e_i, e_j)
- * (ties -> lowest candidate position). cand_items int32 [n_users, C],
- * cand_scores fp32 [n_users, C], item_table bf16 [*, d]; out int32 [n_users, k_out]
+ * (ties -> lowest candidate position; the max term is 0 before the first
+ * pick). cand_items int32 [n_users, C], cand_scores fp32 [n_users, C] (-inf and
+ * NaN count as -FLT_MAX), item_table bf16 [*, d]; out int32 [n_users, k_out]
  * (item ids in selection order). C <= 1024, k_out <= C, d in {64, 128}.
+ * A row whose fp32 sum of squares is 0 has cosine 0 with every row, itself
+ * included, and stays eligible on its score. +inf scores and non-finite item
+ * rows are outside the contract.
  * Candidate ids < 0 are empty slots; ids >= n_items are added to *err (int32
  * device counter, may be NULL) and never picked. A user left without live
  * candidates gets -1 for the remaining picks. n_items = 0 is DR_EINVAL.

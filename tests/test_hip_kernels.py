@@ -11,6 +11,7 @@ import torch
 
 import oracle
 from divrec import _backend, ops
+from mmr_checks import mmr_check_positions as _mmr_check_positions  # the one copy of the replay
 from topk_checks import assert_same_topk, exact_topk, fp32_row_tol, gap_check, int_table
 
 pytestmark = pytest.mark.gpu
@@ -976,35 +977,6 @@ def test_mmr_rerank(lam):
     if lam == 1.0:  # pure relevance: equals top-k by score (ties: lowest position)
         ref = np.take_along_axis(cand, np.argsort(-sc, axis=1, kind="stable")[:, :kout], axis=1)
         assert np.array_equal(got, ref)
-
-
-def _mmr_check_positions(picks, cand, sc, E, lam, tol):
-    """float64 replay that also handles invalid (-1) candidates: each pick must
-    be a live candidate whose MMR value is within tol of the step maximum, and
-    -1 must appear exactly when no live candidate is left."""
-    bad = 0
-    for u in range(cand.shape[0]):
-        valid = cand[u] >= 0
-        X = E[np.where(valid, cand[u], 0)].astype(np.float64)
-        Xn = X / np.linalg.norm(X, axis=1, keepdims=True)
-        sims = Xn @ Xn.T
-        s = sc[u].astype(np.float64)
-        alive = valid.copy()
-        pen = None
-        for it in picks[u]:
-            if not alive.any():
-                bad += int(it != -1)
-                continue
-            val = lam * s - (1 - lam) * (pen if pen is not None else 0.0)
-            val[~alive] = -np.inf
-            hits = np.nonzero(alive & (cand[u] == it))[0]
-            if len(hits) == 0 or val[hits].max() < val.max() - tol:
-                bad += 1
-                continue
-            j = hits[np.argmax(val[hits])]
-            alive[j] = False
-            pen = sims[:, j] if pen is None else np.maximum(pen, sims[:, j])
-    return bad
 
 
 @pytest.mark.parametrize("d,C,kout,lam", [(128, 1000, 100, 0.5), (128, 1024, 100, 0.9),
