@@ -41,8 +41,9 @@ CFLAGS = [
 
 # Per-source flags. ild.hip: MFMA results in VGPRs (the streamed ILD's
 # epilogue reads every Gram element once with VALU; AGPR results each need a
-# v_accvgpr_read first).
-FILE_FLAGS = {"ild.hip": ("-mllvm", "-amdgpu-mfma-vgpr-form")}
+# v_accvgpr_read first); history_dist.hip reads its Gram elements the same way.
+FILE_FLAGS = {"ild.hip": ("-mllvm", "-amdgpu-mfma-vgpr-form"),
+              "history_dist.hip": ("-mllvm", "-amdgpu-mfma-vgpr-form")}
 
 
 def _headers_mtime() -> float:

@@ -19,11 +19,17 @@
 #include <type_traits>
 
 #include "common.h"
+#include "ild_tiles.h"
 
 namespace {
 
 using dr::bf16x8;
 using dr::f32x16;
+using dr::diag_owner;
+using dr::diag_reg;
+using dr::gather_row;
+using dr::gram_tile;
+using dr::pair_dist;
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 template <typename R>
@@ -185,30 +191,14 @@ __device__ __forceinline__ int tile_pos(int t, int col, int k) {
   const int p = 32 * t + col;
   return p < k ? p : 0;
 }
-// This lane's fragments of table row `row` (h = lane >> 5, col = lane & 31
-// throughout).
-template <int D>
-__device__ __forceinline__ void gather_row(const __bf16* __restrict__ E, int64_t row, int h,
-                                           bf16x8 (&f)[D / 16]) {
-  const uint4* src = reinterpret_cast<const uint4*>(E + row * D + 8 * h);
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) f[s] = __builtin_bit_cast(bf16x8, src[2 * s]);
-}
+// gather_row<D>: this lane's fragments of a table row (ild_tiles.h; h = lane >> 5,
+// col = lane & 31 throughout).
 // Tile t of a list whose row ids sit in LDS (the d = 256 kernel).
 template <int D>
 __device__ __forceinline__ void load_tile(const __bf16* __restrict__ E, const int64_t* rows,
                                           int t, int k, bf16x8 (&f)[D / 16]) {
   const int lane = dr::lane_id();
   gather_row<D>(E, rows[tile_pos(t, lane & 31, k)], lane >> 5, f);
-}
-
-template <int D>
-__device__ __forceinline__ f32x16 gram_tile(const bf16x8 (&x)[D / 16], const bf16x8 (&y)[D / 16]) {
-  f32x16 acc = f32x16{};
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[s], y[s], acc, 0, 0, 0);
-  return acc;
 }
 
 // Same, but the zero accumulator is threaded through an empty asm that reads
@@ -226,19 +216,7 @@ __device__ __forceinline__ f32x16 gram_tile_after(const bf16x8 (&x)[D / 16],
   return acc;
 }
 
-// Element (c, c) of a Gram tile is register diag_reg(c) of the lane with
-// col = c in the half-wave that diag_owner(col, h) is true for.
-__device__ constexpr int diag_reg(int col) { return (col & 3) + 4 * (col >> 3); }
-__device__ __forceinline__ bool diag_owner(int col, int h) { return ((col >> 2) & 1) == h; }
-
-// Distance of a pair from its Gram element g and the per-row terms of its two
-// rows: 1/|e| (cosine), unused (dot), |e|^2 (euclidean).
-template <int KIND>
-__device__ __forceinline__ float pair_dist(float g, float wi, float wj) {
-  if constexpr (KIND == DR_ILD_COSINE) return fmaf(-g, wi * wj, 1.f);
-  else if constexpr (KIND == DR_ILD_DOT) return g;
-  else return sqrtf(fmaxf(wi + wj - 2.f * g, 0.f));
-}
+// gram_tile, diag_reg / diag_owner and pair_dist: ild_tiles.h.
 // Register q of one Gram tile in the pair sum: the distance of column j (jv:
 // inside the list) and row i0 + tile_row(q, h), whose term is wi[q], or 0 for
 // a pair that does not count; a diagonal tile keeps its strict upper

@@ -93,6 +93,10 @@ SIGNATURES = {
     "dr_xquad_rerank": (_i32, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _i32, _f32, _p, _p, _p, _p]),
     "dr_aspect_profile": (_i32, [_p, _p, _i64, _p, _i64, _i32, _p, _p, _p]),
     "dr_aspect_coverage": (_i32, [_p, _i32, _i64, _i32, _p, _i64, _i32, _p, _p, _p, _p]),
+    "dr_history_distance": (_i32, [_p, _i64, _i32, _p, _i64, _i32, _p, _p, _i32, _p, _p, _p]),
+    "dr_serendipity_rerank": (_i32, [_p, _p, _i64, _i32, _p, _i64, _i32, _p, _p, _i32, _i32, _f32,
+                                     _p, _p, _p, _p]),
+    "dr_list_item_mean": (_i32, [_p, _i32, _i64, _i32, _p, _i64, _p, _p, _p]),
     "dr_rank_metrics": (_i32, [_p, _i32, _i64, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "dr_catalog_histogram": (_i32, [_p, _i32, _i64, _i32, _i64, _p, _p, _p]),
     "dr_als_solve": (_i32, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _f32, _f32, _p, _p, _p]),

@@ -13,6 +13,13 @@ from .normalized_discounted_cumulative_gain import NDCGScore, normalized_discoun
 from .popularity_rank_correlation_for_items import PRI, avg_rank, rank
 from .precision_at_k import HitRateScore, PrecisionAtKScore, precision_at_k
 from .recall_at_k import RecallAtKScore, recall_at_k
+from .serendipity_scores import (
+    NoveltyScore,
+    SerendipityScore,
+    UnexpectednessScore,
+    novelty_item_values,
+    relevance_flags,
+)
 
 __all__ = [
     "AUCScore",
@@ -24,14 +31,19 @@ __all__ = [
     "IntraListDiversityScore",
     "MeanAveragePrecisionAtKScore",
     "NDCGScore",
+    "NoveltyScore",
     "avg_rank",
     "rank",
     "PRI",
     "PrecisionAtKScore",
     "RecallAtKScore",
+    "SerendipityScore",
+    "UnexpectednessScore",
     "aspect_matrix",
     "average_precision_at_k",
     "normalized_discounted_cumulative_gain",
+    "novelty_item_values",
     "precision_at_k",
     "recall_at_k",
+    "relevance_flags",
 ]

@@ -310,6 +310,68 @@ class _TableModel(RankingModel):
         scores = cand_scores.gather(1, order.gather(1, at))
         return picks, scores.masked_fill_(picks < 0, float("-inf"))
 
+    @torch.no_grad()
+    def recommend_serendipitous(
+        self,
+        k: int,
+        candidates: int,
+        history: Tuple[torch.Tensor, torch.Tensor],
+        lam: float = 0.5,
+        reduce: str = "min",
+        user_ids: Optional[torch.Tensor] = None,
+        user_vectors: Optional[torch.Tensor] = None,
+        item_vectors: Optional[torch.Tensor] = None,
+        precision: str = "fp32",
+        exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+        n_items: Optional[int] = None,
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Serendipity re-ranked lists: the top-``candidates`` items of each
+        user (``score_topk`` with the same ``user_ids`` / ``exclude`` /
+        ``precision`` / ``n_items`` / ``user_vectors`` / ``item_vectors``)
+        re-ranked to the ``k`` best of lam * score + (1 - lam) * distance,
+        distance the ``reduce`` ("min" or "mean") cosine distance of the
+        candidate from the rows of the user's ``history``: a CSR (rowptr int64
+        [n + 1], items int32) with one row per listed user, e.g.
+        ``dataset.exclusion_csr()`` (``ops.serendipity_rerank`` over the bf16
+        item table). ``lam`` weights relevance as in ``recommend_diverse``;
+        ``lam = 1`` and a user without history give the plain top-k. A door of
+        its own: its input is a history, not a ``method``. Returns (items
+        int64 [n, k] in pick order, distances fp32 [n, k]). ``k <= candidates
+        <= min(1024, catalog)`` and an embedding width <= 256, else
+        ValueError."""
+        k, candidates = int(k), int(candidates)
+        if user_vectors is not None and user_ids is not None:
+            raise ValueError("user_vectors are the users to score: user_ids must be None")
+        if reduce not in ("min", "mean"):
+            raise ValueError(f'reduce must be "min" or "mean", got {reduce!r}')
+        if not 0.0 <= float(lam) <= 1.0:
+            raise ValueError(f"lam must be in [0, 1], got {lam}")
+        catalog = self.no_items if item_vectors is None else len(item_vectors)
+        if n_items is not None:
+            catalog = int(n_items)
+        if not 1 <= k <= candidates <= min(MAX_RERANK_CANDIDATES, catalog):
+            raise ValueError(f"need 1 <= k <= candidates <= min({MAX_RERANK_CANDIDATES}, catalog "
+                             f"= {catalog}), got k = {k}, candidates = {candidates}")
+        n_lists = self.no_users if user_ids is None else len(user_ids)
+        if user_vectors is not None:
+            n_lists = len(user_vectors)
+        if (not isinstance(history, (tuple, list)) or len(history) != 2
+                or history[0].dim() != 1 or history[0].numel() != n_lists + 1
+                or history[1].dim() != 1):
+            raise ValueError(f"history must be a CSR (rowptr [{n_lists + 1}], items), one row per "
+                             f"listed user")
+        cand, cand_scores = self.score_topk(candidates, user_ids=user_ids, exclude=exclude,
+                                            precision=precision, n_items=n_items,
+                                            user_vectors=user_vectors, item_vectors=item_vectors)
+        dev = cand.device
+        rows = self._scan_sides("bf16", None, item_vectors, users=False)[1][:catalog]
+        # a history item outside the catalog has no row and is skipped; the
+        # candidates come from the scan and are inside it
+        picks, dist = ops.serendipity_rerank(
+            cand.to(torch.int32), cand_scores, rows, history[0].to(dev, torch.int64),
+            history[1].to(dev, torch.int32), k, lam, reduce, check=False)
+        return picks.to(torch.int64), dist
+
 
 class MatrixFactorization(_TableModel):
     def __init__(self, no_users: int, no_items: int, embedding_dim: int):

@@ -1043,6 +1043,118 @@ def aspect_coverage(recs: torch.Tensor, item_aspects: torch.Tensor, aspect_profi
     return out
 
 
+# --------------------------------------------------------------------------- history distance
+HISTORY_WIDTHS = (32, 64, 128, 256)
+HISTORY_MAX_C = 1024
+_HIST_REDUCE = {"min": 0, "mean": 1}  # enum dr_hist_reduce
+
+
+def _history_csr(rowptr: torch.Tensor, items: torch.Tensor, n: int):
+    _need(rowptr.dtype == torch.int64 and rowptr.dim() == 1 and rowptr.numel() == n + 1,
+          "history rowptr must be int64 [n + 1]")
+    _need(items.dtype == torch.int32 and items.dim() == 1, "history items must be int32 1-D")
+    return rowptr.contiguous(), items.contiguous()
+
+
+def _hist_reduce(reduce: str) -> int:
+    _need(reduce in _HIST_REDUCE, f"reduce must be one of {sorted(_HIST_REDUCE)}")
+    return _HIST_REDUCE[reduce]
+
+
+def history_distance(lists: torch.Tensor, item_table: torch.Tensor, hist_rowptr: torch.Tensor,
+                     hist_items: torch.Tensor, reduce: str = "min",
+                     err: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:
+    """fp32 [n, C]: for every position of ``lists`` (int32 [n, C], C <= 1024) the
+    ``reduce`` ("min" or "mean") over the user's history row of the CSR
+    (rowptr int64 [n + 1], items int32) of 1 - cos(e_item, e_h) on the bf16
+    ``item_table`` (include/divrec_hip.h, dr_history_distance). A user without a
+    valid history entry gets 0, a list id < 0 gets 0, a list id past the table
+    NaN. Ids outside the table (list or history) are counted: into ``err`` when
+    given, else with ``check`` the call reads the count (one sync) and raises
+    IndexError."""
+    dev = B.require_device(lists, item_table, hist_rowptr, hist_items, err)
+    _need(lists.dtype == torch.int32 and lists.dim() == 2, "lists must be int32 [n, C]")
+    n, C = lists.shape
+    _need(1 <= C <= HISTORY_MAX_C, f"C must be in [1, {HISTORY_MAX_C}]")
+    red = _hist_reduce(reduce)
+    table = _bf16_rows(item_table, HISTORY_WIDTHS, "history distance")
+    _need(table.size(0) >= 1, "item_table must not be empty")
+    rowptr, items = _history_csr(hist_rowptr, hist_items, n)
+    out = torch.empty((n, C), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    err, own = _counter(dev, err, check)
+    rc = B.lib().dr_history_distance(
+        lists.contiguous().data_ptr(), n, C, table.data_ptr(), table.size(0), table.size(1),
+        rowptr.data_ptr(), items.data_ptr() if items.numel() else None, red, out.data_ptr(),
+        B.ptr(err), B.stream(dev),
+    )
+    _done(rc, "dr_history_distance", own)
+    return out
+
+
+def serendipity_rerank(
+    cand_items: torch.Tensor, cand_scores: torch.Tensor, item_table: torch.Tensor,
+    hist_rowptr: torch.Tensor, hist_items: torch.Tensor, k_out: int, lam: float = 0.5,
+    reduce: str = "min", err: Optional[torch.Tensor] = None, check: bool = True,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Serendipity re-rank over per-user candidates (int32 [n, C] + fp32 [n, C])
+    -> (items int32 [n, k_out], dist fp32 [n, k_out]): the first ``k_out``
+    candidates in stable descending order of lam * score + (1 - lam) * dist,
+    dist the ``history_distance`` of the candidate from the user's history row
+    (include/divrec_hip.h, dr_serendipity_rerank); ties go to the lowest
+    candidate position. ``lam`` weights relevance as in every re-ranker: lam =
+    1, and a user without history, give the order by score. A list with fewer
+    than ``k_out`` live candidates ends in -1 with dist 0. Ids outside the
+    table are counted as in ``history_distance``."""
+    dev = B.require_device(cand_items, cand_scores, item_table, hist_rowptr, hist_items, err)
+    cand_items, cand_scores, n, C = _candidates(cand_items, cand_scores)
+    _need(1 <= C <= HISTORY_MAX_C, f"C must be in [1, {HISTORY_MAX_C}]")
+    _need(1 <= int(k_out) <= C, "k_out must be in [1, C]")
+    _need(0.0 <= float(lam) <= 1.0, "lam must be in [0, 1]")
+    red = _hist_reduce(reduce)
+    table = _bf16_rows(item_table, HISTORY_WIDTHS, "serendipity re-rank")
+    _need(table.size(0) >= 1, "item_table must not be empty")
+    rowptr, items = _history_csr(hist_rowptr, hist_items, n)
+    out = torch.empty((n, int(k_out)), dtype=torch.int32, device=dev)
+    dist = torch.empty((n, int(k_out)), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out, dist
+    err, own = _counter(dev, err, check)
+    rc = B.lib().dr_serendipity_rerank(
+        cand_items.data_ptr(), cand_scores.data_ptr(), n, C, table.data_ptr(), table.size(0),
+        table.size(1), rowptr.data_ptr(), items.data_ptr() if items.numel() else None, red,
+        int(k_out), float(lam), out.data_ptr(), dist.data_ptr(), B.ptr(err), B.stream(dev),
+    )
+    _done(rc, "dr_serendipity_rerank", own)
+    return out, dist
+
+
+def list_item_mean(recs: torch.Tensor, item_values: torch.Tensor,
+                   err: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:
+    """fp32 [n]: the mean of ``item_values`` (fp32 [n_items]) over the valid
+    entries of each list of ``recs`` [n, k] (int32 or int64; entries < 0 are
+    skipped; a list without a valid entry scores 0), summed in position order.
+    An entry past the table is skipped and counted, into ``err`` when given,
+    else with ``check`` it raises IndexError."""
+    dev = B.require_device(recs, item_values, err)
+    recs, rc_dt = _recs(recs)
+    n, k = recs.shape
+    _need(item_values.dtype == torch.float32 and item_values.dim() == 1,
+          "item_values must be fp32 [n_items]")
+    values = item_values.contiguous()
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    err, own = _counter(dev, err, check)
+    rc = B.lib().dr_list_item_mean(
+        recs.data_ptr() if k else None, rc_dt, n, k, values.data_ptr() if values.numel() else None,
+        values.numel(), out.data_ptr(), B.ptr(err), B.stream(dev),
+    )
+    _done(rc, "dr_list_item_mean", own)
+    return out
+
+
 # --------------------------------------------------------------------------- rank metrics
 def rank_metrics(
     recs: torch.Tensor, pos_rowptr: torch.Tensor, pos_items: torch.Tensor

@@ -351,6 +351,45 @@ def get_diverse_recommendations(dataset: RankingDataset, model: RankingModel,
     return items
 
 
+def get_serendipitous_recommendations(dataset: RankingDataset, model: RankingModel,
+                                      number_of_recommendations: int, candidates: int,
+                                      lam: float = 0.5, reduce: str = "min") -> torch.LongTensor:
+    """Serendipity re-ranked lists of every user of ``dataset`` (LongTensor
+    [U, k] on the CPU, not in the reference): the top-``candidates`` candidates
+    of ``get_model_recommendations``' scan (fp32 scores, frozen items excluded)
+    re-ranked by ``MatrixFactorization.recommend_serendipitous`` to the
+    ``number_of_recommendations`` best of lam * score + (1 - lam) * distance
+    from the user's history, which is its ``frozen`` items
+    (``dataset.exclusion_csr()``). ValueError without ``frozen``, for a model
+    outside the MF fast path, for ragged candidate lists and for a list that
+    ends early, as ``get_diverse_recommendations``."""
+    k, cands = int(number_of_recommendations), int(candidates)
+    if not 1 <= k <= cands <= MAX_RERANK_CANDIDATES:
+        raise ValueError(f"need 1 <= number_of_recommendations <= candidates <= "
+                         f"{MAX_RERANK_CANDIDATES}, got {k} and {cands}")
+    n_users = int(dataset.data.number_of_users)
+    n_items = int(dataset.data.number_of_items)
+    if not (_table_scoring(model) and n_users <= model.no_users and n_items <= model.no_items):
+        raise ValueError("get_serendipitous_recommendations needs a MatrixFactorization model "
+                         "(its own forward) that covers the dataset's users and items")
+    excl = dataset.exclusion_csr()
+    if excl is None:
+        raise ValueError("the users' histories are the frozen interactions: the dataset has none")
+    if n_users == 0:
+        return torch.LongTensor([])
+    c_len = _list_length(dataset, excl, n_users, n_items, cands)
+    if c_len < k:
+        raise ValueError(f"a user has {c_len} candidates, fewer than the {k} recommendations asked for")
+    user_ids = None if n_users == model.no_users else torch.arange(n_users)
+    items, _ = model.recommend_serendipitous(k, c_len, excl, lam=lam, reduce=reduce,
+                                             user_ids=user_ids, exclude=excl, n_items=n_items)
+    items = items.cpu()
+    if bool((items < 0).any()):
+        short = int((items < 0).any(dim=1).sum())
+        raise ValueError(f"{short} lists end before {k} picks, so the lists are ragged")
+    return items
+
+
 def recommendations_score_loop(dataset: RankingDataset, model: RankingModel,
                                losses: List[RecommendationsAwareLoss],
                                number_of_recommendations: int):

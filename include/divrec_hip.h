@@ -635,6 +635,73 @@ int dr_aspect_coverage(const void* recs, int rec_dtype, int64_t n_users, int k,
                        float* out, int32_t* err, dr_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Distance of list items from the user's own history through the item
+ * embeddings (unexpectedness and serendipity, Kaminskas & Bridge, TiiS 2016;
+ * no reference symbol):
+ *   out[u, p] = reduce_{h in H_u, 0 <= h < n_items} (1 - cos(e_{r[u,p]}, e_h))
+ * lists int32 [n_users, C] (finished lists or candidate lists), 1 <= C <= 1024;
+ * item_table bf16 [n_items, d], d in {32, 64, 128, 256}; the history is a CSR
+ * (hist_rowptr int64 [n_users + 1], hist_items int32, rows of any length; the
+ * exclusion CSR of dr_score_topk is one; hist_items may be NULL when every row
+ * is empty); reduce DR_HIST_MIN or DR_HIST_MEAN; out fp32 [n_users, C].
+ * The cosine is the fp32 Gram accumulation of the bf16 rows times 1/|e| of
+ * both rows, 1 - g (w_h w_c) in one fused multiply-add. A row whose fp32 sum
+ * of squares is 0 has cosine 0 with every row, so its distance is 1
+ * (dr_mmr_rerank's rule). History entries outside [0, n_items) are skipped and
+ * counted in *err (int32 device counter, may be NULL); their rows are never
+ * read. A user with no valid history entry gets 0 for every valid list id,
+ * for both reductions. List ids < 0 are empty slots and get 0; list ids >=
+ * n_items get NaN (also for a user without history) and are counted in *err,
+ * their rows never read. MEAN divides the sum by the number of valid history
+ * entries; the sum runs in fp32 within a 32-row history tile and in double
+ * across tiles. MIN is exact in its inputs and independent of the order of
+ * the history. Duplicate history entries count once each (MEAN) and change
+ * nothing (MIN). No float atomics: the result is bitwise reproducible.
+ * n_users = 0 is a no-op success; bad sizes (C, n_users, n_items outside
+ * [0, 2^31), reduce) are DR_EINVAL and another d is DR_EUNSUPPORTED, both
+ * before any HIP call; n_items = 0 with users present is DR_EINVAL.
+ * Launch: a persistent grid (DR_KNOB_SCAN_SLOTS caps the CUs, as for
+ * dr_mmr_rerank); one wave serves a user when C <= 128, a workgroup above;
+ * one user's history is never split across workgroups. */
+enum dr_hist_reduce { DR_HIST_MIN = 0, DR_HIST_MEAN = 1 };
+int dr_history_distance(const int32_t* lists, int64_t n_users, int C, const void* item_table,
+                        int64_t n_items, int d, const int64_t* hist_rowptr,
+                        const int32_t* hist_items, int reduce, float* out, int32_t* err,
+                        dr_stream_t stream);
+
+/* Serendipity re-rank: per user the first k_out candidates in stable
+ * descending order of
+ *   value_i = lambda * score_i + (1 - lambda) * dist_i
+ * (fp32, two multiplies and one add, no fused multiply-add; ties -> lowest
+ * candidate position), dist_i the dr_history_distance of candidate i, computed
+ * by the same device function: out_dist (fp32 [n_users, k_out], may be NULL),
+ * the picks' distances, is bitwise what dr_history_distance returns for the
+ * same inputs. There is no greedy loop: one register sort per user of the keys
+ * (value, position). -inf and NaN scores count as -FLT_MAX; +inf scores are
+ * outside the contract. out_items int32 [n_users, k_out]: item ids in that
+ * order. Candidate ids < 0 are never live; ids >= n_items are never live and
+ * are added to *err. With fewer than k_out live candidates the remaining picks
+ * are -1 with out_dist 0. 1 <= k_out <= C <= 1024, lambda in [0, 1]; n_items
+ * = 0 with users present is DR_EINVAL. lambda = 1, and a user without valid
+ * history, each give the stable order by score exactly. The other arguments,
+ * the error codes and the launch are dr_history_distance's. */
+int dr_serendipity_rerank(const int32_t* cand_items, const float* cand_scores, int64_t n_users,
+                          int C, const void* item_table, int64_t n_items, int d,
+                          const int64_t* hist_rowptr, const int32_t* hist_items, int reduce,
+                          int k_out, float lambda, int32_t* out_items, float* out_dist,
+                          int32_t* err, dr_stream_t stream);
+
+/* Per-list mean of a per-item value (novelty: self-information or popularity
+ * complement of the items): out[u] = mean of item_values[recs[u, p]] over the
+ * valid entries of recs [n_users, k] (rec_dtype DR_I32 or DR_I64); item_values
+ * fp32 [n_items]. Entries < 0 are skipped; entries >= n_items are skipped and
+ * counted in *err. A list without a valid entry scores 0. The sum runs in
+ * position order in fp32 and is divided once: reproducible. */
+int dr_list_item_mean(const void* recs, int rec_dtype, int64_t n_users, int k,
+                      const float* item_values, int64_t n_items, float* out, int32_t* err,
+                      dr_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Implicit-feedback ALS row solve (Hu, Koren, Volinsky, ICDM 2008; no
  * reference symbol): one half-step of alternating least squares, and the
  * fold-in of rows the model has never seen. fixed_table Y fp32 [n_fixed_rows,
